@@ -1,7 +1,13 @@
 #!/usr/bin/env python
 """bench.py -- DDPM reverse steps/s of PDR's dual-path PointNet++ on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints one JSON line (`value`, `ms_per_step`, ...).
+--dump-outputs DIR then also writes what the timed path computed in its last step: x, the (B, 2048, 3) clouds after
+the last timed step, as DIR/x.npy (float32; DIR/x_rank<r>.npy per rank for N > 1).  Inputs, weights and the noise key
+are seeded, so the same arguments give the same inputs on every run.
+--full adds everything beyond the headline: the end-of-job metric evaluation + gather, and at N=1 the legs listed below.
 
 N > 1 without a torch.distributed environment: bench.py re-launches itself under
 `python -m torch.distributed.run --nproc-per-node N` (one process per GPU, rendezvous on
@@ -15,8 +21,8 @@ Each rank owns its own batch (weak scaling, no data-path collective); the K time
 bracketed by barrier + synchronize and the MAX over ranks is reported.  After the timed region
 every rank evaluates Chamfer / F1 / EMD of its batch against synthetic ground truth and the
 (n, 5) metric records travel through ONE all-gather (generation.gather_records: RCCL for N > 1),
-exactly the collective the generation harness uses at the end of a job.
-Rank 0 prints one JSON line.  At N=1 rank 0 also reports
+exactly the collective the generation harness uses at the end of a job -- with --full.
+Rank 0 prints one JSON line.  With --full, at N=1 rank 0 also reports
   * `roofline`: the dominant hand-written kernel of THIS run (selected from HIP-event timings of
     every C-ABI launch of an eager step), against its roof;
   * `cpu_baseline`: the CPU port (this repo's PyTorch-CPU network over the C oracle ops) on
@@ -64,11 +70,16 @@ def parse(argv=None):
     ap.add_argument("--single-stream", action="store_true",
                     help="profiling: the two halves of every block on ONE stream, so that every kernel has the chip to "
                          "itself (tools/profile_round.sh's serial pass); never the headline")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true", help="skip the live roofline of the dominant kernel")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure beyond the headline: metric evaluation + gather and, at N=1, the roofline, "
+                         "extras and CPU-baseline legs (a plain run times the steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write x after the last timed step as DIR/x.npy (float32; x_rank<r>.npy per rank for N > 1)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="(--full) skip the live roofline of the dominant kernel")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the split-f16 / config-3 / config-5 legs (N=1 only)")
-    ap.add_argument("--cpu-seconds", type=float, default=20.0, help="budget of the CPU baseline sample")
+                    help="(--full) skip the split-f16 / config-3 / config-5 legs (N=1 only)")
+    ap.add_argument("--cpu-seconds", type=float, default=20.0, help="(--full) budget of the CPU baseline sample")
     ap.add_argument("--dry", action="store_true",
                     help="host-logic check without a GPU (tests): gloo backend, no sampler, synthetic metric "
                          "records through the same gather")
@@ -307,6 +318,16 @@ def config5_fastdpm_refine(device, B):
     return out
 
 
+def dump_outputs(directory, x, rank, world):
+    """What a caller of the timed path receives after its last step: the clouds x (B, N, 3), float32 (786 KB at B=32).
+    All ranks together write at most 64 MB: a larger --batch keeps its first clouds."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    keep = max(1, (64 << 20) // world // (x[0].numel() * 4))
+    name = "x.npy" if world == 1 else "x_rank%d.npy" % rank
+    np.save(os.path.join(directory, name), x[:keep].detach().float().cpu().numpy())
+
+
 def rank_times(elapsed, steps, world, device=None):
     """(max over ranks of `elapsed`, per-rank report) -- the contract's MAX, plus every rank's own ms per step so that the
     first real N-GPU run shows whether one straggler or the host side limits weak scaling."""
@@ -422,14 +443,8 @@ def main():
     elapsed, per_rank = rank_times(elapsed, args.steps, world, device)
     x_now = sampler._x
     assert bool(torch.isfinite(x_now).all()), "non-finite samples"
-
-    # ---- end-of-job metric reduction (outside the timed region): the ONE collective of the path
-    t0 = time.perf_counter()
-    rec = metric_records(x_now.clone(), label, rank)
-    allrec, counts = G.gather_records(rec, return_counts=True)
-    torch.cuda.synchronize(device)
-    gather_s = time.perf_counter() - t0
-    summary = G.summarize(allrec)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, x_now, rank, world)
 
     ms_per_step = elapsed / args.steps * 1e3
     value = world * B * args.steps / elapsed                       # cloud-steps/s, whole job
@@ -463,15 +478,24 @@ def main():
                       "replayed": dict(getattr(sampler, "mode_counts", {})),
                       "tiles_walked_frac": None if getattr(sampler, "walked_share", None) is None
                       else round(sampler.walked_share, 4)},
-        "ranks_seen": int(sum(1 for c in counts if c > 0)), "records_gathered": int(allrec.shape[0]),
-        # (after the gather: the collective's own view of the job -- the first real N-GPU run verifies itself)
-        "world_size_after_gather": dist.get_world_size() if (world > 1 and dist.is_initialized()) else 1,
-        "metric_gather": {"collective": "all_gather of (n,5) f32 records [cd_t, cd_p, f1, emd, label]",
-                          "backend": "nccl (RCCL)" if world > 1 else "none (1 rank)",
-                          "eval_plus_gather_ms": round(gather_s * 1e3, 2),
-                          "avg_cd": summary["avg_cd"], "avg_emd": summary["avg_emd"]},
     }
-    solo = world == 1 and rank == 0
+    if args.full:
+        # ---- end-of-job metric reduction (outside the timed region): the ONE collective of the path
+        t0 = time.perf_counter()
+        rec = metric_records(x_now.clone(), label, rank)
+        allrec, counts = G.gather_records(rec, return_counts=True)
+        torch.cuda.synchronize(device)
+        gather_s = time.perf_counter() - t0
+        summary = G.summarize(allrec)
+        out.update({
+            "ranks_seen": int(sum(1 for c in counts if c > 0)), "records_gathered": int(allrec.shape[0]),
+            # (after the gather: the collective's own view of the job -- the first real N-GPU run verifies itself)
+            "world_size_after_gather": dist.get_world_size() if (world > 1 and dist.is_initialized()) else 1,
+            "metric_gather": {"collective": "all_gather of (n,5) f32 records [cd_t, cd_p, f1, emd, label]",
+                              "backend": "nccl (RCCL)" if world > 1 else "none (1 rank)",
+                              "eval_plus_gather_ms": round(gather_s * 1e3, 2),
+                              "avg_cd": summary["avg_cd"], "avg_emd": summary["avg_emd"]}})
+    solo = world == 1 and rank == 0 and args.full          # the legs beyond the headline
     if solo and not args.no_roofline:
         try:
             from tools.kernel_roofline import dominant_kernel_roofline

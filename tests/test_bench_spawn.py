@@ -101,7 +101,7 @@ def test_driver_launch_line_with_one_rank_on_the_gpu():
            if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
                         "--master-addr", "127.0.0.1", "--master-port", "29733", os.path.join(ROOT, "bench.py"),
-                        "--gpus", "1", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-roofline",
+                        "--gpus", "1", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-roofline",
                         "--no-extras"], env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -109,3 +109,20 @@ def test_driver_launch_line_with_one_rank_on_the_gpu():
     out = json.loads(lines[0])
     assert out["n_gpus"] == 1 and out["steps"] == 3 and out["scaling"] == "weak" and out["value"] > 0
     assert out["ranks_seen"] == 1 and out["world_size_after_gather"] == 1
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_steps_and_dumps_the_last_step(tmp_path):
+    """A plain `bench.py --gpus 1` run: the headline line only (no leg of --full), `steps` / `ms_per_step` as asked, and
+    --dump-outputs writes the clouds after the last timed step."""
+    r = _run(["--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path)], timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    out = json.loads(lines[0])
+    assert out["steps"] == 3 and out["ms_per_step"] > 0 and out["unit"] == "cloud-steps/s" and out["dtype"] == "f32"
+    assert abs(out["value"] - 32 * 1e3 / out["ms_per_step"]) < 1e-3 * out["value"]
+    assert not {"metric_gather", "roofline", "cpu_baseline", "split_f16", "trajectory"} & set(out)
+    import numpy as np
+    x = np.load(str(tmp_path / "x.npy"))
+    assert x.shape == (32, 2048, 3) and x.dtype == np.float32 and np.isfinite(x).all()
