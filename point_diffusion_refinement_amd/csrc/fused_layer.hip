@@ -1075,6 +1075,10 @@ int plan_layer(const pdr_layer_in_t* in, long P, int Cin, const float* Wt, int l
              !in->pre_relu && !in->post_relu && !in->oadd && Y && ldy % 4 == 0 &&
              reinterpret_cast<uintptr_t>(Y) % 16 == 0 && ldw >= ((Cout + 3) & ~3) && ldy >= ((Cout + 3) & ~3) &&
              P < (1L << 31);
+  // what only the wave-specialised kernels carry: kNN-form gathered sources (the caller materialises instead) and a
+  // tile subset (128-row tiles).  Decided here so that the plan refuses exactly what the launch refuses.
+  if (knn && !pl->ws) return PDR_EUNSUPPORTED;
+  if (in->tile_list && (!in->n_tiles || !pl->ws || t.tm != 128)) return PDR_EUNSUPPORTED;
   return PDR_OK;
 }
 }  // namespace

@@ -1073,8 +1073,11 @@ namespace pdr {
 bool fused_layer_ws_supported(int id, bool radd, bool gath, const pdr_layer_in_t& in, int Cin) {
   if (Cin > kMaxCin) return false;   // identity scale / shift / add arrays cover kMaxCin channels
   if (in.wrow0 && gath) return false;   // weighted statistics: the plain-source instantiations (and the uniform kernel)
-  // a row map of the per-query term: gathered instantiations read it per 32-row block only (one query per block)
-  if (in.oadd_rows && gath && (in.oadd_div < 32 || in.rows_per_batch % 128 != 0)) return false;
+  // a row map of the per-query term: gathered instantiations read it per 32-row block only (one query per block), on
+  // full row tiles only (their per-row path of a partial last tile has no row map) -- whole tiles of the variant: 256
+  // rows for 0 / 1, 128 for the rest (variant 5's 64-row tiles included: such calls stay on the uniform-wave kernel)
+  const int tm_map = id <= 1 ? 256 : 128;
+  if (in.oadd_rows && gath && (in.oadd_div < 32 || in.rows_per_batch % tm_map != 0)) return false;
   if (id == 3 || id == 6 || id > 8) return false;   // 128 x 160 (80 accumulators) and 32-row tiles: uniform-wave kernel
   bool knn = false;
   for (int sg = 0; sg < in.n_seg; ++sg) knn = knn || in.seg[sg].g_r1 != nullptr;

@@ -1,0 +1,94 @@
+"""pdr_fused_layer_plan over the whole dispatch table, host only (fake device addresses; nothing is launched).
+
+Every cell of the table below -- kernel family x tile variant x source form -- must be reached with PDR_OK by at least
+one targeted case of tests/layer_cases.py, the wave-specialised and uniform-wave cells also by one whose last row
+tile is partial; and the plan must refuse (PDR_EUNSUPPORTED) exactly what pdr_fused_layer refuses: kNN-gathered
+sources without a wave-specialised instantiation and tile subsets without the wave-specialised 128-row kernel.
+"""
+from point_diffusion_refinement_amd import _lib
+from tests import layer_cases as lc
+
+# The required cells, from plan_layer (csrc/fused_layer.hip) and fused_layer_ws_supported (csrc/fused_layer_ws.hip):
+#   wave-specialised: variants 0 1 2 4 5 7 8 (3 and 6 have no instantiation) x every source form;
+#   uniform-wave (fused_ws = 0): variants 0..8 x plain / residual / ball-gathered (no kNN form there);
+#   scalar (non-float4) staging, the thin kernel, the right-sized deep launches 4 / 5 / 6, paired 128-row launches.
+REQUIRED = ([("ws", v, f) for v in lc.WS_VARIANTS for f in lc.FORMS] +
+            [("uniform", v, f) for v in lc.UNIFORM_VARIANTS for f in ("plain", "residual", "ball")] +
+            [("scalar",), ("thin",), ("deep", 4), ("deep", 5), ("deep", 6)] +
+            [("pair", v) for v in lc.PAIR_VARIANTS])
+NEED_PARTIAL = {c for c in REQUIRED if c[0] in ("ws", "uniform")}
+
+
+def _expect_refusal(L, out_ws_possible):
+    """The launch's refusal rule, stated on the case: kNN-gathered sources or a tile subset need the wave-specialised
+    kernel (and, for the subset, its 128-row tiles)."""
+    c = L.case
+    knn = c.form in ("knn", "knn_res")
+    return (knn and not out_ws_possible) or (c.tile_list and (not out_ws_possible or L.tm != 128))
+
+
+def test_plan_reaches_every_dispatch_cell_and_refuses_what_the_launch_refuses():
+    lib = _lib.load()
+    reached, partial = {}, set()
+    checked = 0
+    for opt, opts in lc.OPTION_SETS.items():
+        with lc.options(opts):
+            targeted = lc.targeted(opt)
+            for case in targeted + lc.random_cases(opt, 40):
+                L = lc.build(case, None)
+                rc, out = L.plan()
+                assert rc in (_lib.PDR_OK, _lib.PDR_EUNSUPPORTED), (case.label(), rc)
+                if rc == _lib.PDR_OK:
+                    # what the plan reports agrees with the case ...
+                    assert out[2] == int(case.form in ("residual", "ball_res", "knn_res")), case.label()
+                    assert out[3] == {"ball": 1, "ball_res": 1, "knn": 2, "knn_res": 2}.get(case.form, 0), case.label()
+                    assert out[1] == lib.pdr_fused_layer_variant(case.rpb, case.Cout)
+                    # ... and the plan never promises a launch pdr_fused_layer would refuse
+                    assert not _expect_refusal(L, bool(out[0])), (opt, case.label(), out)
+                    if case.pair:
+                        L2 = lc.build(lc.pair_case(case), None)
+                        rc2, out2 = L2.plan()
+                        assert rc2 == _lib.PDR_OK and out2[0] == 1 and out2[1] == out[1], (case.label(), out2)
+                else:
+                    # a refusal is one of the two rules: with the wave-specialised kernels off, or on a shape they
+                    # cannot take, the same case is refused; with them on it is planned on them
+                    assert case.form in ("knn", "knn_res") or case.tile_list, (opt, case.label())
+                    assert opt.startswith("fused_ws=0") or case.tile_list or case.form in ("knn", "knn_res")
+                    if opt == "fused_ws=0":
+                        with lc.options({"fused_ws": 1}):
+                            rc1, out1 = L.plan()
+                        assert rc1 != _lib.PDR_OK or not _expect_refusal(L, bool(out1[0]))
+                cell = lc.cell_of(L, rc, out)
+                if cell is not None and case in targeted:
+                    reached.setdefault(cell, []).append("%s: %s" % (opt, case.label()))
+                    if case.rpb % L.tm:
+                        partial.add(cell)
+                checked += 1
+            # the fused_ws = 0 refusals are there
+            if opt == "fused_ws=0":
+                knn = [c for c in lc.targeted(opt) if c.form == "knn" or c.tile_list]
+                assert knn and all(lc.build(c, None).plan()[0] == _lib.PDR_EUNSUPPORTED for c in knn)
+    missing = [c for c in REQUIRED if c not in reached]
+    no_partial = sorted(NEED_PARTIAL - partial)
+    print("\n%d cases planned, %d cells reached:" % (checked, len(reached)))
+    for cell in sorted(reached, key=str):
+        print("  %-28s %4d cases  e.g. %s" % (cell, len(reached[cell]), reached[cell][0]))
+    assert not missing, "dispatch cells no targeted case reaches: %s" % missing
+    assert not no_partial, "cells never reached with a partial last tile: %s" % no_partial
+
+
+def test_advisor_case_leaves_the_wave_specialised_kernel():
+    """narrow_kc32 = 0, 384 rows per cloud (a 256-row tile and a half tile), ball-gathered source, per-query term
+    through a row map: the gathered wave-specialised instantiations have no row map on a partial tile, so the call
+    goes to the uniform-wave kernel (out[0] = 0), which maps every row; with 512 rows (whole tiles) it stays."""
+    for Cout, variant in ((32, 0), (64, 1)):
+        with lc.options({"narrow_kc32": 0}):
+            L = lc.build(lc.advisor_case(Cout), None)
+            rc, out = L.plan()
+            assert rc == _lib.PDR_OK and out[1] == variant and out[0] == 0, out
+            whole = lc.advisor_case(Cout)
+            whole.rpb = 512
+            rc, out = lc.build(whole, None).plan()
+            assert rc == _lib.PDR_OK and out[1] == variant and out[0] == 1, out
+        rc, out = lc.build(lc.advisor_case(Cout), None).plan()       # default 128-row tiles: whole tiles, stays
+        assert rc == _lib.PDR_OK and out[0] == 1 and out[1] in (7, 8), out
