@@ -29,7 +29,7 @@
 // Roofline: at the dominant shapes (P = 2.1 M positions, C = 32-96) the layer moves
 // 4 (Cin + Cout) bytes per position for 2 Cin Cout flops: 5-20 flop/B, i.e. HBM-bound
 // (machine balance ~25 flop/B at the 157 TF fp32-MFMA peak).
-#include "pdr_common.h"
+#include "layer_tiles.h"
 
 #include <cstdlib>
 
@@ -924,61 +924,78 @@ __global__ __launch_bounds__(256) void fused_layer_thin_kernel(const float* __re
 }  // namespace
 
 namespace {
-// Tile shapes.  "Tall" shapes stack all four waves along the rows and give every wave the full
-// output width (one column block => the input is read exactly once): used whenever Cout <= 160.
-// Wide outputs use 128 x 128 tiles (2 x 2 waves) over a 2-D grid.
-struct TileCfg { int tm, tn, id; };
+using pdr::LayerSource;
+using pdr::Tile;
+
+// Tile selection: the id of a variant of pdr::kTiles (layer_tiles.h; its height and width are tile_tm / tile_tn
+// there).  "Tall" shapes stack all four waves along the rows and give every wave the full output width (one column
+// block => the input is read exactly once): used whenever Cout <= 160.  Wide outputs use 128 x 128 tiles (2 x 2
+// waves) over a 2-D grid.
 // narrow outputs: 128-row tiles staged in 32-channel chunks (ids 7, 8) instead of 256-row tiles in 16-channel
 // chunks (ids 0, 1): a row of <= 32 channels is then fetched as ONE whole 128-byte line (the half-line fetches of
 // the 16-channel chunks were re-read from HBM).  Option narrow_kc32 = 0: the 256-row tiles.
 inline bool narrow_kc32() { return pdr::option(pdr::OPT_NARROW_KC32) != 0; }
-inline TileCfg pick_tile(int rows_per_batch, int Cout) {
-  if (narrow_kc32() && rows_per_batch >= 128 && Cout <= 32) return {128, 32, 7};
-  if (narrow_kc32() && rows_per_batch >= 128 && Cout <= 64) return {128, 64, 8};
-  if (rows_per_batch >= 256 && Cout <= 32) return {256, 32, 0};
-  if (rows_per_batch >= 256 && Cout <= 64) return {256, 64, 1};
-  if (rows_per_batch >= 128 && Cout <= 96) return {128, 96, 2};
-  if (rows_per_batch >= 128 && Cout > 128 && Cout <= 160) return {128, 160, 3};
+inline int pick_tile(int rows_per_batch, int Cout) {
+  if (narrow_kc32() && rows_per_batch >= 128 && Cout <= 32) return 7;
+  if (narrow_kc32() && rows_per_batch >= 128 && Cout <= 64) return 8;
+  if (rows_per_batch >= 256 && Cout <= 32) return 0;
+  if (rows_per_batch >= 256 && Cout <= 64) return 1;
+  if (rows_per_batch >= 128 && Cout <= 96) return 2;
+  if (rows_per_batch >= 128 && Cout > 128 && Cout <= 160) return 3;
   // (64-row tiles for the deep levels, whose 128 x 128 tiling has fewer jobs than the 512 resident workgroups -- B = 32:
   // 16 k rows x 128 columns = 128 jobs -- measured 8.72-8.77 vs 8.75-8.77 ms per step in round 4: no gain, not taken)
-  if (rows_per_batch >= 128) return {128, 128, 4};
-  if (rows_per_batch >= 64) return {64, 128, 5};
-  return {32, 128, 6};
+  if (rows_per_batch >= 128) return 4;
+  if (rows_per_batch >= 64) return 5;
+  return 6;
 }
 }  // namespace
 
 extern "C" int pdr_fused_layer_tile_rows(int rows_per_batch, int Cout) {
   if (rows_per_batch <= 0 || Cout <= 0) return 0;
-  return pick_tile(rows_per_batch, Cout).tm;
+  return pdr::tile_tm(pick_tile(rows_per_batch, Cout));
 }
 
-// which kernel instantiation pdr_fused_layer() launches (0..6, see pick_tile); lets profilers and
-// bench.py attribute a launch to its kernel symbol
+// which kernel instantiation pdr_fused_layer() launches (0..8: the index into pdr::kTiles, see pick_tile); lets
+// profilers and bench.py attribute a launch to its kernel symbol
 extern "C" int pdr_fused_layer_variant(int rows_per_batch, int Cout) {
   if (rows_per_batch <= 0 || Cout <= 0) return -1;
-  return pick_tile(rows_per_batch, Cout).id;
+  return pick_tile(rows_per_batch, Cout);
 }
 
-// The dispatch decision of pdr_fused_layer, shared with pdr_fused_layer_plan (profilers / bench.py attribute a
-// call to the kernel symbol it launches without duplicating these rules).
+// The dispatch decision of pdr_fused_layer: plan_layer() is the only place that decides or refuses; pdr_fused_layer
+// launches what it names, pdr_fused_layer_plan reports it (profilers / bench.py attribute a call to the kernel
+// symbol it launches without duplicating these rules), the pair and f16x3 entry points build on its `ws`.
 namespace {
+enum class Family {
+  Thin,         // fused_layer_thin_kernel
+  DeepSplitK,   // right-sized tiny layer, the waves split the K walk (`deep` = 6: 32 x 32 / 4 ways, 5: 64 x 32 / 2 ways)
+  Deep,         // right-sized tiny layer (`deep` = 6: 32 x 128, 5: 64 x 64, 4: 128 x 64; 128-channel chunks)
+  Ws,           // fused_layer_ws_kernel of the tile variant
+  Uniform       // fused_layer_kernel of the tile variant
+};
+
 struct LayerPlan {
-  TileCfg t;
-  bool vec, gath, radd, ws, knn, thin;
+  Family family;
+  int id, tm;     // tile variant (pdr::kTiles) and its rows
+  LayerSource src;
+  bool vec;       // float4 staging
+  bool ws;        // the wave-specialised kernel of `id` carries this input (whatever `family` pdr_fused_layer takes)
+  bool thin;      // the thin kernel could run this call (it does when there is no `partial` and no tile subset)
   long ntiles;
-  int ncol;
-  // right-sized launch of a tiny layer (see pdr_fused_layer): 0 = none, 5 / 4 = the 64 x 64 / 128 x 64 tiles of the
-  // uniform-wave kernel with 128-channel chunks in place of the wave-specialised 64 x 128 / 128 x 128 ones, 6 = 32-row
-  // tiles with 128-channel chunks
+  int ncol;       // column blocks of the tile variant
+  // right-sized launch of a tiny layer: 0 = none, else the tile variant whose launch it replaces (4, 5, 6); their
+  // shapes are outside pdr::kTiles and named where pdr_fused_layer launches them
   int deep;
+  int deep_tn;    // column-block width of the Deep / DeepSplitK launch (0: none)
 };
 
 bool deep_chunks() { return pdr::option(pdr::OPT_DEEP_CHUNKS) != 0; }
 
 bool use_ws_kernels() { return pdr::option(pdr::OPT_FUSED_WS) != 0; }
 
+// has_partial: the call collects statistics (the thin kernel has none).  Y may be null (pooled / planning callers).
 int plan_layer(const pdr_layer_in_t* in, long P, int Cin, const float* Wt, int ldw, int Cout, const float* Y,
-               int ldy, LayerPlan* pl) {
+               int ldy, bool has_partial, LayerPlan* pl) {
   if (!in || !Wt || P < 0 || Cin <= 0 || Cout <= 0 || in->n_seg < 1 || in->n_seg > 4 || ldw < Cout ||
       (Y && ldy < Cout))
     return PDR_EINVAL;
@@ -994,61 +1011,55 @@ int plan_layer(const pdr_layer_in_t* in, long P, int Cin, const float* Wt, int l
   if (in->oadd && (in->oadd_div < 1 || (in->oadd_div & (in->oadd_div - 1)) || in->oadd_ld < Cout))
     return PDR_EINVAL;
   if (in->ss_ld != 0 && in->ss_ld < Cin) return PDR_EINVAL;
-  const TileCfg t = pick_tile(in->rows_per_batch, Cout);
+  const int id = pick_tile(in->rows_per_batch, Cout), tm = pdr::tile_tm(id);
   for (int sg = 0; sg < in->n_seg; ++sg) {
     // every tile must start on a multiple of the broadcast divisor
     const int d = in->seg[sg].row_div;
-    if (in->rows_per_batch % d != 0 || (in->rows_per_batch > t.tm && t.tm % d != 0)) return PDR_EUNSUPPORTED;
+    if (in->rows_per_batch % d != 0 || (in->rows_per_batch > tm && tm % d != 0)) return PDR_EUNSUPPORTED;
   }
   const long nb = P / in->rows_per_batch;
   // rows of `partial` per batch element: at least its tiles (a smaller stride would fold tiles of two batch elements
   // into one row); weighted statistics come with a weight
-  if (in->partial_tpb > 0 && in->partial_tpb < (in->rows_per_batch + t.tm - 1) / t.tm) return PDR_EINVAL;
-  pl->t = t;
-  pl->ntiles = nb * ((in->rows_per_batch + t.tm - 1) / t.tm);
-  pl->ncol = (Cout + t.tn - 1) / t.tn;
+  if (in->partial_tpb > 0 && in->partial_tpb < (in->rows_per_batch + tm - 1) / tm) return PDR_EINVAL;
+  pl->id = id;
+  pl->tm = tm;
+  pl->ntiles = nb * ((in->rows_per_batch + tm - 1) / tm);
+  pl->ncol = (Cout + pdr::tile_tn(id) - 1) / pdr::tile_tn(id);
+  const LayerSource src = pdr::layer_source(*in);
+  const bool gath = src.gath, radd = src.radd;
   // vector (float4) A staging needs every source 16-B aligned with a leading dimension that is a
   // multiple of 4 floats and rows padded to a multiple of 4 channels
   auto aligned = [](const float* p, int ld, int C) {
     return reinterpret_cast<uintptr_t>(p) % 16 == 0 && ld % 4 == 0 && ld >= ((C + 3) & ~3);
   };
-  bool vec = true, gath = false;
+  bool vec = true;
   for (int sg = 0; sg < in->n_seg; ++sg) {
     const pdr_seg_t& g = in->seg[sg];
     vec = vec && aligned(g.ptr, g.ld, g.C);
     if (g.gV) {
-      gath = true;
       vec = vec && aligned(g.gV, g.g_ldv, g.C) && (!g.gV0 || aligned(g.gV0, g.g_ldv, g.C));
       if (g.row_div != 1 || g.g_nsrc <= 0) return PDR_EINVAL;
     }
   }
-  const bool radd = in->rseg.ptr != nullptr;
   if (radd) {
     vec = vec && in->n_seg == 1 && aligned(in->rseg.ptr, in->rseg.ld, Cin);
-    if (in->rseg.gV) {
-      gath = true;
+    if (in->rseg.gV)
       vec = vec && aligned(in->rseg.gV, in->rseg.g_ldv, Cin) &&
             (!in->rseg.gV0 || aligned(in->rseg.gV0, in->rseg.g_ldv, Cin));
-    }
   }
   if (gath) {
     // gathered sources exist only in the vector path; one shared index array, K a power of two that
     // divides the row tile so that a tile starts on a query boundary
     if (!vec || !in->gidx || in->gK <= 0 || (in->gK & (in->gK - 1)) || in->rows_per_batch % in->gK != 0 ||
-        t.tm % in->gK != 0)
+        tm % in->gK != 0)
       return PDR_EUNSUPPORTED;
     for (int sg = 0; sg < in->n_seg; ++sg)
       if (in->seg[sg].gV && in->gcnt && !in->seg[sg].gV0) return PDR_EINVAL;
   }
-  bool knn = false;
-  for (int sg = 0; sg < in->n_seg; ++sg) knn = knn || in->seg[sg].g_r1 || in->seg[sg].g_r2;
-  knn = knn || (in->rseg.gV && (in->rseg.g_r1 || in->rseg.g_r2));
-  pl->knn = knn;
+  pl->src = src;
   pl->vec = vec;
-  pl->gath = gath;
-  pl->radd = radd;
   // steady-state layers (float4-staged sources): wave-specialised kernel where an instantiation exists
-  pl->ws = use_ws_kernels() && vec && pdr::fused_layer_ws_supported(t.id, radd, gath, *in, Cin);
+  pl->ws = use_ws_kernels() && vec && pdr::fused_layer_ws_supported(id, src, *in, Cin);
   // TINY layers (round 5; option deep_chunks = 0: never).  The per-point layers of the deep levels are launches of a few
   // dozen workgroups, each a serial walk over the input channels: their time is (chunks) x (load latency) + (MFMAs per
   // wave) x 64 cycles on a chip that is half to seven eighths empty.  Where every workgroup of the launch is resident
@@ -1057,45 +1068,97 @@ int plan_layer(const pdr_layer_in_t* in, long P, int Cin, const float* Wt, int l
   //   32-row tiles (batch elements of < 64 rows: 16 points per cloud), <= 256 jobs          -> 32 x 128, 128-channel chunks
   //   64-row tiles (64 .. 127 rows: 64 points), plain sources, <= 512 jobs of 64 x 64       -> 64 x 64,  128-channel chunks
   //   128-row tiles (128 .. 511 rows at B = 32: 256 points), plain sources, <= 128 jobs     -> 128 x 64, 128-channel chunks
-  // and, for plain sources, the first two narrower still with the K walk split among the waves (pdr_fused_layer):
-  // 32 x 32 tiles / 4 ways, 64 x 32 tiles / 2 ways.
   // (128 for the last: beyond that every CU already holds a workgroup and the matrix pipes are what the launch waits
   // for -- bound at 256 / 512: step 5.85 / 6.06 ms against 5.79 at 128.)  Measured alone on the
   // chip, B = 32: 16 rows 512 -> 512 35.8 -> 27.6 us, 64 rows 256 -> 256 16.6 -> 14.0, 256 rows 128 -> 128 16.2 -> 12.5,
   // 256 -> 256 26.7 -> 22.0, 512 rows 128 -> 128 17.2 -> 13.6; step 6.03 -> 5.87 ms (profiles/r5_tiny_layers_ab.txt).
   pl->deep = 0;
   if (deep_chunks() && Cin > 64 && !in->tile_list) {
-    if (t.id == 6 && pl->ntiles * pl->ncol <= pdr::option(pdr::OPT_DEEP_JOBS32)) pl->deep = 6;
-    else if (t.id == 5 && vec && !gath && pl->ntiles * ((Cout + 63) / 64) <= pdr::option(pdr::OPT_DEEP_JOBS64)) pl->deep = 5;
-    else if (t.id == 4 && vec && !gath && pl->ntiles * pl->ncol <= 128) pl->deep = 4;
+    if (id == 6 && pl->ntiles * pl->ncol <= pdr::option(pdr::OPT_DEEP_JOBS32)) pl->deep = 6;
+    else if (id == 5 && vec && !gath && pl->ntiles * ((Cout + 63) / 64) <= pdr::option(pdr::OPT_DEEP_JOBS64)) pl->deep = 5;
+    else if (id == 4 && vec && !gath && pl->ntiles * pl->ncol <= 128) pl->deep = 4;
   }
-  // <= 4 input channels, nothing to apply on the way in, 16-byte rows on both sides: the thin kernel (statistics
-  // are decided by the caller: pdr_fused_layer uses it only without `partial`)
+  // ... and, for plain sources, the waves of the first two split the K walk (fused_layer_kernel's KS): 4 ways on
+  // 32 x 32 tiles for the 32-row family (16 rows per cloud: a wave's chain of Cin / 2 MFMAs was most of the launch),
+  // 2 ways on 64 x 32 tiles for the 64-row family; not for the 128-row family (128 x 32 tiles, measured: 256 rows
+  // 256 -> 256 22.0 -> 54.3 us -- four times the workgroups re-reading the same 128 input rows).  Option deep_ks = 0:
+  // no split (A/B).
+  const bool split_k = (pl->deep == 6 || pl->deep == 5) && pdr::option(pdr::OPT_DEEP_KS) != 0 && vec && !gath;
+  pl->deep_tn = !pl->deep ? 0 : split_k ? 32 : pl->deep == 6 ? 128 : 64;
+  // <= 4 input channels, nothing to apply on the way in, 16-byte rows on both sides: the thin kernel (it collects no
+  // statistics: taken only without `partial`)
   pl->thin = vec && Cin <= 4 && in->n_seg == 1 && !gath && !radd && !in->scale && !in->shift && !in->add &&
              !in->pre_relu && !in->post_relu && !in->oadd && Y && ldy % 4 == 0 &&
              reinterpret_cast<uintptr_t>(Y) % 16 == 0 && ldw >= ((Cout + 3) & ~3) && ldy >= ((Cout + 3) & ~3) &&
              P < (1L << 31);
   // what only the wave-specialised kernels carry: kNN-form gathered sources (the caller materialises instead) and a
-  // tile subset (128-row tiles).  Decided here so that the plan refuses exactly what the launch refuses.
-  if (knn && !pl->ws) return PDR_EUNSUPPORTED;
-  if (in->tile_list && (!in->n_tiles || !pl->ws || t.tm != 128)) return PDR_EUNSUPPORTED;
+  // tile subset (128-row tiles)
+  if (src.knn_marked && !pl->ws) return PDR_EUNSUPPORTED;
+  if (in->tile_list && (!in->n_tiles || !pl->ws || tm != 128)) return PDR_EUNSUPPORTED;
+  pl->family = pl->thin && !has_partial && !in->tile_list ? Family::Thin
+               : split_k                                   ? Family::DeepSplitK
+               : pl->deep                                  ? Family::Deep
+               : pl->ws                                    ? Family::Ws
+                                                           : Family::Uniform;
   return PDR_OK;
+}
+
+// everything of a uniform-wave launch but the grid and the template arguments
+struct LayerArgs {
+  hipStream_t s; const pdr_layer_in_t& in; int Cin; const float* Wt; int ldw; const float* bias; int Cout;
+  float* Y; int ldy; float* partial; int relu_col0, n_row_tiles; PoolArgs pool;
+};
+
+template <class T, bool RADD, bool VEC, bool GATH, bool POOL = false, int KS = 1>
+void launch_k(dim3 grid, const LayerArgs& a) {
+  hipLaunchKernelGGL((fused_layer_kernel<T::RT, T::CT, T::WR, T::WC, T::KC, RADD, VEC, GATH, POOL, KS>), grid,
+                     dim3(256), 0, a.s, a.in, a.Cin, a.Wt, a.ldw, a.bias, a.Cout, a.Y, a.ldy, a.partial, a.relu_col0,
+                     a.n_row_tiles, a.pool);
+}
+
+// residual x (gathered / float4-staged / scalar-staged sources)
+template <class T>
+void launch_form(dim3 grid, const LayerArgs& a, const LayerPlan& pl) {
+  if (pl.src.radd) {
+    if (pl.src.gath) launch_k<T, true, true, true>(grid, a);
+    else if (pl.vec) launch_k<T, true, true, false>(grid, a);
+    else launch_k<T, true, false, false>(grid, a);
+  } else {
+    if (pl.src.gath) launch_k<T, false, true, true>(grid, a);
+    else if (pl.vec) launch_k<T, false, true, false>(grid, a);
+    else launch_k<T, false, false, false>(grid, a);
+  }
+}
+
+// float4-staged plain sources (the right-sized tiny layers), the K walk split KS ways
+template <class T, int KS = 1>
+void launch_plain(dim3 grid, const LayerArgs& a, bool radd) {
+  if (radd) launch_k<T, true, true, false, false, KS>(grid, a);
+  else launch_k<T, false, true, false, false, KS>(grid, a);
+}
+
+// grid of the uniform-wave kernel: enough workgroups to fill 256 CUs a few times over; the rest is covered by the
+// grid stride
+dim3 uniform_grid(long ntiles, int ncol) {
+  const long cap = (256L * 6 + ncol - 1) / ncol;
+  return dim3(static_cast<unsigned>(ntiles > cap ? cap : ntiles), static_cast<unsigned>(ncol));
 }
 }  // namespace
 
 // out[0..6] = {wave-specialised kernel?, tile variant id, residual source?, gathered source (0 no / 1 ball / 2 kNN),
 // float4 staging?, split-f16 arithmetic?, thin kernel when called without `partial`?} of the launch
-// pdr_fused_layer would make for these arguments.
+// pdr_fused_layer would make for these arguments: the plan of a call WITH `partial`, and whether the thin kernel
+// would replace it without.
 extern "C" int pdr_fused_layer_plan(const pdr_layer_in_t* in, long P, int Cin, const float* Wt, int ldw, int Cout,
                                     const float* Y, int ldy, int* out) {
   if (!out) return PDR_EINVAL;
   LayerPlan pl;
-  const int rc = plan_layer(in, P, Cin, Wt, ldw, Cout, Y, ldy, &pl);
+  const int rc = plan_layer(in, P, Cin, Wt, ldw, Cout, Y, ldy, true, &pl);
   if (rc != PDR_OK) return rc;
-  out[0] = pl.ws && pl.deep != 4 && pl.deep != 5;
-  out[1] = pl.t.id;
-  out[2] = pl.radd;
-  out[3] = pl.gath ? (pl.knn ? 2 : 1) : 0;
+  out[0] = pl.family == Family::Ws;
+  out[1] = pl.id;
+  out[2] = pl.src.radd;
+  out[3] = pl.src.gath ? (pl.src.knn_marked ? 2 : 1) : 0;
   out[4] = pl.vec;
   out[5] = 0;
   out[6] = pl.thin;
@@ -1111,107 +1174,45 @@ extern "C" int pdr_fused_layer(const pdr_layer_in_t* in, long P, int Cin, const 
                                int relu_col0, pdr_stream_t stream) {
   if (!Y) return PDR_EINVAL;
   LayerPlan pl;
-  const int prc = plan_layer(in, P, Cin, Wt, ldw, Cout, Y, ldy, &pl);
+  const int prc = plan_layer(in, P, Cin, Wt, ldw, Cout, Y, ldy, partial != nullptr, &pl);
   if (prc != PDR_OK) return prc;
   if (P == 0) return PDR_OK;
-  const TileCfg t = pl.t;
-  const bool vec = pl.vec, gath = pl.gath, radd = pl.radd;
   hipStream_t s = pdr::as_stream(stream);
-  const long ntiles = pl.ntiles;
-  const int ncol = pl.ncol;
-  // enough workgroups to fill 256 CUs a few times over; the rest is covered by the grid stride
-  long gx = ntiles;
-  const long cap = (256L * 6 + ncol - 1) / ncol;
-  if (gx > cap) gx = cap;
-  const dim3 grid(static_cast<unsigned>(gx), static_cast<unsigned>(ncol));
-  const int nt = static_cast<int>(ntiles);
-  // a tile subset (pdr_layer_in_t.tile_list) is walked by the wave-specialised kernels with 128-row tiles only
-  if (in->tile_list && (!in->n_tiles || !pl.ws || t.tm != 128)) return PDR_EUNSUPPORTED;
-  if (pl.thin && !partial && !in->tile_list) {
-    const int c4n = (Cout + 3) / 4;
-    int qshift = 3;                                    // 8 .. 64 column quads per row of threads
-    while (qshift < 6 && (1 << qshift) < c4n) ++qshift;
-    const int ql = 1 << qshift, rows_per_block = (256 >> qshift) * 8;
-    const dim3 tgrid(static_cast<unsigned>((P + rows_per_block - 1) / rows_per_block),
-                     static_cast<unsigned>((c4n + ql - 1) / ql));
-    hipLaunchKernelGGL(fused_layer_thin_kernel, tgrid, dim3(256), 0, s, in->seg[0].ptr, in->seg[0].ld,
-                       __builtin_ctz(in->seg[0].row_div), Cin, Wt, ldw, bias, Cout, Y, ldy, P, qshift);
-    return pdr::check_launch();
-  }
-  // ... and their waves split the K walk (fused_layer_kernel's KS): 4 ways on 32 x 32 tiles for the 32-row family (16
-  // rows per cloud: a wave's chain of Cin / 2 MFMAs was most of the launch), 2 ways on 64 x 32 tiles for the 64-row
-  // family; not for the 128-row family (128 x 32 tiles, measured: 256 rows 256 -> 256 22.0 -> 54.3 us -- four times the
-  // workgroups re-reading the same 128 input rows).  Plain sources.  Option deep_ks = 0: no split (A/B).
-  const bool deep_ks = pdr::option(pdr::OPT_DEEP_KS) != 0;
-  if ((pl.deep == 6 || pl.deep == 5) && deep_ks && vec && !gath) {
-#define PDR_DEEP_KS_LAUNCH(RT, WR, WC, KSV, TNV)                                                                    \
-  do {                                                                                                                \
-    const dim3 gk(static_cast<unsigned>(ntiles), static_cast<unsigned>((Cout + TNV - 1) / TNV));                      \
-    if (radd)                                                                                                         \
-      hipLaunchKernelGGL((fused_layer_kernel<RT, 1, WR, WC, 128, true, true, false, false, KSV>), gk, dim3(256), 0, s, \
-                         *in, Cin, Wt, ldw, bias, Cout, Y, ldy, partial, relu_col0, nt);                              \
-    else                                                                                                              \
-      hipLaunchKernelGGL((fused_layer_kernel<RT, 1, WR, WC, 128, false, true, false, false, KSV>), gk, dim3(256), 0, s, \
-                         *in, Cin, Wt, ldw, bias, Cout, Y, ldy, partial, relu_col0, nt);                              \
-  } while (0)
-    if (pl.deep == 6) PDR_DEEP_KS_LAUNCH(1, 1, 1, 4, 32);
-    else PDR_DEEP_KS_LAUNCH(1, 2, 1, 2, 32);
-#undef PDR_DEEP_KS_LAUNCH
-    return pdr::check_launch();
-  }
-  if (pl.deep == 5 || pl.deep == 4) {   // right-sized tiny layer (plan_layer)
-    const dim3 g64(static_cast<unsigned>(ntiles), static_cast<unsigned>((Cout + 63) / 64));
-#define PDR_DEEP(RT, WR)                                                                                          \
-  do {                                                                                                            \
-    if (radd)                                                                                                     \
-      hipLaunchKernelGGL((fused_layer_kernel<RT, 1, WR, 2, 128, true, true, false>), g64, dim3(256), 0, s, *in, Cin, \
-                         Wt, ldw, bias, Cout, Y, ldy, partial, relu_col0, nt);                                    \
-    else                                                                                                          \
-      hipLaunchKernelGGL((fused_layer_kernel<RT, 1, WR, 2, 128, false, true, false>), g64, dim3(256), 0, s, *in, Cin, \
-                         Wt, ldw, bias, Cout, Y, ldy, partial, relu_col0, nt);                                    \
-  } while (0)
-    if (pl.deep == 5) PDR_DEEP(1, 2);
-    else PDR_DEEP(2, 2);
-#undef PDR_DEEP
-    return pdr::check_launch();
-  }
-  if (pl.ws &&
-      pdr::launch_fused_layer_ws(t.id, radd, gath, *in, Cin, Wt, ldw, bias, Cout, Y, ldy, partial, relu_col0, nt,
-                                 ncol, s))
-    return pdr::check_launch();
-  // kNN-form gathered sources exist in the wave-specialised kernel only: the caller materialises instead
-  if (pl.knn || in->tile_list) return PDR_EUNSUPPORTED;
-#define PDR_LAUNCH_V(RT, CT, WR, WC, KC, RADD, VEC, GATH)                                            \
-  hipLaunchKernelGGL((fused_layer_kernel<RT, CT, WR, WC, KC, RADD, VEC, GATH>), grid, dim3(256), 0, s, \
-                     *in, Cin, Wt, ldw, bias, Cout, Y, ldy, partial, relu_col0, nt)
-#define PDR_LAUNCH(RT, CT, WR, WC, KC)                                \
-  do {                                                                \
-    if (radd) {                                                       \
-      if (gath) PDR_LAUNCH_V(RT, CT, WR, WC, KC, true, true, true);   \
-      else if (vec) PDR_LAUNCH_V(RT, CT, WR, WC, KC, true, true, false); \
-      else PDR_LAUNCH_V(RT, CT, WR, WC, KC, true, false, false);      \
-    } else {                                                          \
-      if (gath) PDR_LAUNCH_V(RT, CT, WR, WC, KC, false, true, true);  \
-      else if (vec) PDR_LAUNCH_V(RT, CT, WR, WC, KC, false, true, false); \
-      else PDR_LAUNCH_V(RT, CT, WR, WC, KC, false, false, false);     \
-    }                                                                 \
-  } while (0)
-  switch (t.id) {
-    case 0: PDR_LAUNCH(2, 1, 4, 1, 16); break;
-    case 1: PDR_LAUNCH(2, 2, 4, 1, 16); break;
-    case 2: PDR_LAUNCH(1, 3, 4, 1, 32); break;
-    case 3: PDR_LAUNCH(1, 5, 4, 1, 32); break;
-    case 4: PDR_LAUNCH(2, 2, 2, 2, 32); break;
-    case 5: PDR_LAUNCH(1, 2, 2, 2, 32); break;
-    case 7: PDR_LAUNCH(1, 1, 4, 1, 32); break;
-    case 8: PDR_LAUNCH(1, 2, 4, 1, 32); break;
-    default:
-      if (pl.deep == 6) PDR_LAUNCH(1, 1, 1, 4, 128);   // right-sized tiny layer (plan_layer)
-      else PDR_LAUNCH(1, 1, 1, 4, 32);
+  const int nt = static_cast<int>(pl.ntiles);
+  const LayerArgs a{s, *in, Cin, Wt, ldw, bias, Cout, Y, ldy, partial, relu_col0, nt, PoolArgs()};
+  // the right-sized launches: one workgroup per job
+  auto deep_grid = [&] {
+    return dim3(static_cast<unsigned>(pl.ntiles), static_cast<unsigned>((Cout + pl.deep_tn - 1) / pl.deep_tn));
+  };
+  switch (pl.family) {
+    case Family::Thin: {
+      const int c4n = (Cout + 3) / 4;
+      int qshift = 3;                                    // 8 .. 64 column quads per row of threads
+      while (qshift < 6 && (1 << qshift) < c4n) ++qshift;
+      const int ql = 1 << qshift, rows_per_block = (256 >> qshift) * 8;
+      const dim3 tgrid(static_cast<unsigned>((P + rows_per_block - 1) / rows_per_block),
+                       static_cast<unsigned>((c4n + ql - 1) / ql));
+      hipLaunchKernelGGL(fused_layer_thin_kernel, tgrid, dim3(256), 0, s, in->seg[0].ptr, in->seg[0].ld,
+                         __builtin_ctz(in->seg[0].row_div), Cin, Wt, ldw, bias, Cout, Y, ldy, P, qshift);
+      break;
+    }
+    case Family::DeepSplitK:
+      if (pl.deep == 6) launch_plain<Tile<1, 1, 1, 1, 128>, 4>(deep_grid(), a, pl.src.radd);   // 32 x 32, 4 ways
+      else launch_plain<Tile<1, 1, 2, 1, 128>, 2>(deep_grid(), a, pl.src.radd);                // 64 x 32, 2 ways
+      break;
+    case Family::Deep:
+      if (pl.deep == 6) launch_form<Tile<1, 1, 1, 4, 128>>(uniform_grid(pl.ntiles, pl.ncol), a, pl);   // 32 x 128
+      else if (pl.deep == 5) launch_plain<Tile<1, 1, 2, 2, 128>>(deep_grid(), a, pl.src.radd);           // 64 x 64
+      else launch_plain<Tile<2, 1, 2, 2, 128>>(deep_grid(), a, pl.src.radd);                             // 128 x 64
+      break;
+    case Family::Ws:
+      pdr::launch_fused_layer_ws(pl.id, pl.src, *in, Cin, Wt, ldw, bias, Cout, Y, ldy, partial, relu_col0, nt, pl.ncol,
+                                 s);
+      break;
+    case Family::Uniform:
+      pdr::with_tile(pl.id, [&](auto t) { launch_form<decltype(t)>(uniform_grid(pl.ntiles, pl.ncol), a, pl); });
       break;
   }
-#undef PDR_LAUNCH
-#undef PDR_LAUNCH_V
   return pdr::check_launch();
 }
 
@@ -1226,21 +1227,23 @@ extern "C" int pdr_fused_layer_pair(const pdr_layer_in_t* in, long P, const pdr_
                                     pdr_stream_t stream) {
   if (!Y || !Y2 || !in || !in2) return PDR_EINVAL;
   LayerPlan pl, pl2;
-  int rc = plan_layer(in, P, Cin, Wt, ldw, Cout, Y, ldy, &pl);
+  int rc = plan_layer(in, P, Cin, Wt, ldw, Cout, Y, ldy, partial != nullptr, &pl);
   if (rc != PDR_OK) return rc;
-  rc = plan_layer(in2, P2, Cin, Wt, ldw, Cout, Y2, ldy2, &pl2);
+  rc = plan_layer(in2, P2, Cin, Wt, ldw, Cout, Y2, ldy2, partial2 != nullptr, &pl2);
   if (rc != PDR_OK) return rc;
   if (P == 0 || P2 == 0) return PDR_EUNSUPPORTED;
   if ((partial == nullptr) != (partial2 == nullptr)) return PDR_EINVAL;
   // the first problem decides the tile shape: a listed launch of 128-row tiles; the second runs on the same tiles
   // (its batch elements may be shorter than a tile: partial tiles, one row of `partial2` per 128 rows)
-  if (!in->tile_list || !in->n_tiles || pl.t.tm != 128 || !pl.ws || !pl.vec || !pl2.vec || pl.radd || pl2.radd ||
-      pl2.gath || pl.knn || in2->tile_list)
+  if (!in->tile_list || !pl.ws || !pdr::tile_has_pair(pl.id) || !pl.vec || !pl2.vec || pl.src.radd || pl2.src.radd ||
+      pl2.src.gath || pl.src.knn_marked || in2->tile_list)
     return PDR_EUNSUPPORTED;
-  const int tpb2 = (in2->rows_per_batch + 127) / 128;
+  const int tpb2 = (in2->rows_per_batch + pl.tm - 1) / pl.tm;
   if (in2->partial_tpb > 0 && in2->partial_tpb < tpb2) return PDR_EINVAL;
   for (int sg = 0; sg < in2->n_seg; ++sg)
     if (in2->seg[sg].row_div != 1) return PDR_EUNSUPPORTED;
+  // the second problem on the FIRST's tile variant (pl2 is its plan on a variant of its own), without an index array
+  if (in2->gidx || !pdr::fused_layer_ws_supported(pl.id, pl2.src, *in2, Cin)) return PDR_EUNSUPPORTED;
   pdr::WsTwin tw;
   tw.in[1] = *in2;
   tw.Y[1] = Y2;
@@ -1248,36 +1251,32 @@ extern "C" int pdr_fused_layer_pair(const pdr_layer_in_t* in, long P, const pdr_
   tw.ldy[1] = ldy2;
   tw.n_row_tiles[1] = static_cast<int>((P2 / in2->rows_per_batch) * tpb2);
   tw.gx = 0;
-  if (!pdr::launch_fused_layer_ws_pair(pl.t.id, pl.gath, *in, Cin, Wt, ldw, bias, Cout, Y, ldy, partial, relu_col0,
-                                       static_cast<int>(pl.ntiles), pl.ncol, tw, pdr::as_stream(stream)))
-    return PDR_EUNSUPPORTED;
+  pdr::launch_fused_layer_ws_pair(pl.id, pl.src.gath, *in, Cin, Wt, ldw, bias, Cout, Y, ldy, partial, relu_col0,
+                                  static_cast<int>(pl.ntiles), pl.ncol, tw, pdr::as_stream(stream));
   return pdr::check_launch();
 }
 
 // pdr_fused_layer with SPLIT-f16 arithmetic (opt-in): both GEMM operands are split into f16 hi + lo parts and the
 // product is accumulated as xh wh + xh wl + xl wh on v_mfma_f32_32x32x16_f16 with fp32 accumulation (~22 mantissa
 // bits kept).  Wp = weight image of pdr-side packing (see include/pdr_hip.h), nchunks = K-chunks per column block.
-// Only the wave-specialised tile variants 4, 5 and 8 carry this mode: PDR_EUNSUPPORTED otherwise (callers fall back to
-// the exact fp32 entry point).
+// Only the wave-specialised tile variants of pdr::tile_has_split carry this mode: PDR_EUNSUPPORTED otherwise (callers
+// fall back to the exact fp32 entry point).
 extern "C" int pdr_fused_layer_f16x3(const pdr_layer_in_t* in, long P, int Cin, const void* Wp, int nchunks,
                                      const float* bias, int Cout, float* Y, int ldy, float* partial,
                                      int relu_col0, pdr_stream_t stream) {
   if (!Y || !Wp || nchunks <= 0 || reinterpret_cast<uintptr_t>(Wp) % 16 != 0) return PDR_EINVAL;
   LayerPlan pl;
   // (the fp32 weight arguments of the plan are placeholders: alignment-clean dummies)
-  const int prc = plan_layer(in, P, Cin, reinterpret_cast<const float*>(Wp), (Cout + 3) & ~3, Cout, Y, ldy, &pl);
+  const int prc = plan_layer(in, P, Cin, reinterpret_cast<const float*>(Wp), (Cout + 3) & ~3, Cout, Y, ldy,
+                             partial != nullptr, &pl);
   if (prc != PDR_OK) return prc;
   if (P == 0) return PDR_OK;
-  if (!pl.ws || (pl.t.id != 4 && pl.t.id != 5 && pl.t.id != 8)) return PDR_EUNSUPPORTED;
-  // a tile subset is a list of 128-row tile numbers with its length on the device (as pdr_fused_layer)
-  if (in->tile_list && (!in->n_tiles || pl.t.tm != 128)) return PDR_EUNSUPPORTED;
+  if (!pl.ws || !pdr::tile_has_split(pl.id)) return PDR_EUNSUPPORTED;
   int nch = 0;
   for (int s = 0; s < in->n_seg; ++s) nch += (in->seg[s].C + 31) / 32;
   if (nch != nchunks) return PDR_EINVAL;   // the image was packed for another segment structure
-  if (!pdr::launch_fused_layer_ws(pl.t.id, pl.radd, pl.gath, *in, Cin, reinterpret_cast<const float*>(Wp), nchunks,
-                                  bias, Cout, Y, ldy, partial, relu_col0, static_cast<int>(pl.ntiles), pl.ncol,
-                                  pdr::as_stream(stream), true))
-    return PDR_EUNSUPPORTED;
+  pdr::launch_fused_layer_ws(pl.id, pl.src, *in, Cin, reinterpret_cast<const float*>(Wp), nchunks, bias, Cout, Y, ldy,
+                             partial, relu_col0, static_cast<int>(pl.ntiles), pl.ncol, pdr::as_stream(stream), true);
   return pdr::check_launch();
 }
 
@@ -1292,44 +1291,63 @@ bool pool_patch_args_ok(const pdr_layer_in_t& in, int D, const float* out, int l
   return in.patch_w != nullptr && in.patch_ld >= D && D % 4 == 0 && in.patch_ld % 4 == 0 && ldo % 4 == 0 &&
          reinterpret_cast<uintptr_t>(in.patch_values) % 16 == 0 && reinterpret_cast<uintptr_t>(out) % 16 == 0;
 }
-}  // namespace
 
-// pdr_fused_layer_pool with the score conv on split-f16 arithmetic (packed weight image as pdr_fused_layer_f16x3);
-// the 128-column wave-specialised tiles only: PDR_EUNSUPPORTED otherwise (the caller uses the exact entry point).
-extern "C" int pdr_fused_layer_pool_f16x3(const pdr_layer_in_t* in, long P, int Cin, const void* Wp, int nchunks,
-                                          const float* bias, int D, const float* values, int ldv,
-                                          const float* vscale, const float* vshift, int v_relu,
-                                          const int* counts, int K, float* out, int ldo, pdr_stream_t stream) {
-  if (!in || !Wp || nchunks <= 0 || reinterpret_cast<uintptr_t>(Wp) % 16 != 0 || !values || !out || P <= 0 ||
-      Cin <= 0 || D <= 0 || in->n_seg < 1 || in->n_seg > 4 || ldv < D || ldo < D)
+// What the two pooled entry points share: validation of everything but the weights (`weights_ok`: the caller's own
+// check of its weight arguments, part of the first PDR_EINVAL), the tile and the grid arithmetic.  nch = 32-channel
+// chunks of the segments (the packed weight image's structure).
+struct PoolPlan {
+  int id, tm, ncol, nch;
+  long ntiles;
+  bool vec;   // float4 staging possible (every pooled kernel needs it; refused after the EINVAL checks)
+};
+int plan_pool(const pdr_layer_in_t* in, long P, int Cin, bool weights_ok, int D, const float* values, int ldv, int K,
+              const float* out, int ldo, PoolPlan* pp) {
+  if (!in || !weights_ok || !values || !out || P <= 0 || Cin <= 0 || D <= 0 || in->n_seg < 1 || in->n_seg > 4 ||
+      ldv < D || ldo < D)
     return PDR_EINVAL;
   if (!pool_patch_args_ok(*in, D, out, ldo)) return PDR_EINVAL;
   if (!(K == 8 || K == 16 || K == 32)) return PDR_EUNSUPPORTED;
   if (in->rseg.ptr || in->oadd) return PDR_EUNSUPPORTED;
-  int ctot = 0, nch = 0;
-  bool vec = true;
+  int ctot = 0;
+  pp->nch = 0;
+  pp->vec = true;
   for (int s = 0; s < in->n_seg; ++s) {
     const pdr_seg_t& g = in->seg[s];
     if (!g.ptr || g.C <= 0 || g.row_div != 1 || g.gV) return PDR_EUNSUPPORTED;
-    vec = vec && reinterpret_cast<uintptr_t>(g.ptr) % 16 == 0 && g.ld % 4 == 0 && g.ld >= ((g.C + 3) & ~3);
+    pp->vec = pp->vec && reinterpret_cast<uintptr_t>(g.ptr) % 16 == 0 && g.ld % 4 == 0 && g.ld >= ((g.C + 3) & ~3);
     ctot += g.C;
-    nch += (g.C + 31) / 32;
+    pp->nch += (g.C + 31) / 32;
   }
   if (ctot != Cin || in->rows_per_batch <= 0 || P % in->rows_per_batch != 0 || in->rows_per_batch % 32 != 0)
     return PDR_EINVAL;
-  if (nch != nchunks) return PDR_EINVAL;   // the image was packed for another segment structure
-  if (!vec || !use_ws_kernels()) return PDR_EUNSUPPORTED;
-  const TileCfg t = pick_tile(in->rows_per_batch, D);
-  if ((t.id != 4 && t.id != 5 && t.id != 8) || in->rows_per_batch % t.tm != 0) return PDR_EUNSUPPORTED;
-  if (in->tile_list && (!in->n_tiles || t.tm != 128)) return PDR_EUNSUPPORTED;
-  const long nb = P / in->rows_per_batch;
-  const long ntiles = nb * ((in->rows_per_batch + t.tm - 1) / t.tm);
-  const int ncol = (D + t.tn - 1) / t.tn;
-  PoolArgs pa{values, vscale, vshift, counts, out, ldv, ldo, K, v_relu};
-  if (!pdr::launch_fused_layer_ws(t.id, false, false, *in, Cin, reinterpret_cast<const float*>(Wp), nchunks, bias, D,
-                                  nullptr, 0, nullptr, D, static_cast<int>(ntiles), ncol, pdr::as_stream(stream), true,
-                                  &pa))
-    return PDR_EUNSUPPORTED;
+  pp->id = pick_tile(in->rows_per_batch, D);
+  pp->tm = pdr::tile_tm(pp->id);
+  pp->ntiles = P / in->rows_per_batch * ((in->rows_per_batch + pp->tm - 1) / pp->tm);
+  pp->ncol = (D + pdr::tile_tn(pp->id) - 1) / pdr::tile_tn(pp->id);
+  return PDR_OK;
+}
+}  // namespace
+
+// pdr_fused_layer_pool with the score conv on split-f16 arithmetic (packed weight image as pdr_fused_layer_f16x3);
+// the wave-specialised tiles of pdr::tile_has_split only: PDR_EUNSUPPORTED otherwise (the caller uses the exact entry
+// point).
+extern "C" int pdr_fused_layer_pool_f16x3(const pdr_layer_in_t* in, long P, int Cin, const void* Wp, int nchunks,
+                                          const float* bias, int D, const float* values, int ldv,
+                                          const float* vscale, const float* vshift, int v_relu,
+                                          const int* counts, int K, float* out, int ldo, pdr_stream_t stream) {
+  PoolPlan pp;
+  const int rc = plan_pool(in, P, Cin, Wp && nchunks > 0 && reinterpret_cast<uintptr_t>(Wp) % 16 == 0, D, values, ldv,
+                           K, out, ldo, &pp);
+  if (rc != PDR_OK) return rc;
+  if (pp.nch != nchunks) return PDR_EINVAL;   // the image was packed for another segment structure
+  if (!pp.vec || !use_ws_kernels()) return PDR_EUNSUPPORTED;
+  if (!pdr::tile_has_split(pp.id) || in->rows_per_batch % pp.tm != 0) return PDR_EUNSUPPORTED;
+  if (in->tile_list && (!in->n_tiles || pp.tm != 128)) return PDR_EUNSUPPORTED;
+  const LayerSource src = pdr::layer_source(*in);
+  if (!pdr::fused_layer_ws_supported(pp.id, src, *in, Cin)) return PDR_EUNSUPPORTED;
+  const PoolArgs pa{values, vscale, vshift, counts, out, ldv, ldo, K, v_relu};
+  pdr::launch_fused_layer_ws(pp.id, src, *in, Cin, reinterpret_cast<const float*>(Wp), nchunks, bias, D, nullptr, 0,
+                             nullptr, D, static_cast<int>(pp.ntiles), pp.ncol, pdr::as_stream(stream), true, &pa);
   return pdr::check_launch();
 }
 
@@ -1338,58 +1356,26 @@ extern "C" int pdr_fused_layer_pool(const pdr_layer_in_t* in, long P, int Cin, c
                                     const float* vscale, const float* vshift, int v_relu,
                                     const int* counts, int K, float* out, int ldo,
                                     pdr_stream_t stream) {
-  if (!in || !Wt || !values || !out || P <= 0 || Cin <= 0 || D <= 0 || in->n_seg < 1 || in->n_seg > 4 ||
-      ldw < D || ldw % 4 != 0 || reinterpret_cast<uintptr_t>(Wt) % 16 != 0 || ldv < D || ldo < D)
-    return PDR_EINVAL;
-  if (!pool_patch_args_ok(*in, D, out, ldo)) return PDR_EINVAL;
-  if (!(K == 8 || K == 16 || K == 32)) return PDR_EUNSUPPORTED;
-  if (in->rseg.ptr || in->oadd) return PDR_EUNSUPPORTED;
-  int ctot = 0;
-  bool vec = true;
-  for (int s = 0; s < in->n_seg; ++s) {
-    const pdr_seg_t& g = in->seg[s];
-    if (!g.ptr || g.C <= 0 || g.row_div != 1 || g.gV) return PDR_EUNSUPPORTED;
-    vec = vec && reinterpret_cast<uintptr_t>(g.ptr) % 16 == 0 && g.ld % 4 == 0 && g.ld >= ((g.C + 3) & ~3);
-    ctot += g.C;
-  }
-  if (ctot != Cin || in->rows_per_batch <= 0 || P % in->rows_per_batch != 0 || in->rows_per_batch % 32 != 0)
-    return PDR_EINVAL;
-  if (!vec) return PDR_EUNSUPPORTED;
-  const TileCfg t = pick_tile(in->rows_per_batch, D);
-  if (in->tile_list && (!in->n_tiles || t.tm != 128)) return PDR_EUNSUPPORTED;
+  PoolPlan pp;
+  const int rc = plan_pool(in, P, Cin, Wt && ldw >= D && ldw % 4 == 0 && reinterpret_cast<uintptr_t>(Wt) % 16 == 0, D,
+                           values, ldv, K, out, ldo, &pp);
+  if (rc != PDR_OK) return rc;
+  if (!pp.vec) return PDR_EUNSUPPORTED;
+  if (in->tile_list && (!in->n_tiles || pp.tm != 128)) return PDR_EUNSUPPORTED;
   hipStream_t s = pdr::as_stream(stream);
-  const long nb = P / in->rows_per_batch;
-  const long ntiles = nb * ((in->rows_per_batch + t.tm - 1) / t.tm);
-  const int ncol = (D + t.tn - 1) / t.tn;
-  long gx = ntiles;
-  const long cap = (256L * 6 + ncol - 1) / ncol;
-  if (gx > cap) gx = cap;
-  const dim3 grid(static_cast<unsigned>(gx), static_cast<unsigned>(ncol));
-  const int nt = static_cast<int>(ntiles);
-  PoolArgs pa{values, vscale, vshift, counts, out, ldv, ldo, K, v_relu};
+  const PoolArgs pa{values, vscale, vshift, counts, out, ldv, ldo, K, v_relu};
+  const int nt = static_cast<int>(pp.ntiles);
   // wave-specialised kernels carry the pooled epilogue for the tile shapes whose rows tile whole queries
-  if (use_ws_kernels() && in->rows_per_batch % t.tm == 0 &&
-      pdr::launch_fused_layer_ws(t.id, false, false, *in, Cin, Wt, ldw, bias, D, nullptr, 0, nullptr, D, nt, ncol, s,
-                                 false, &pa))
+  const LayerSource src = pdr::layer_source(*in);
+  if (use_ws_kernels() && in->rows_per_batch % pp.tm == 0 && pdr::fused_layer_ws_supported(pp.id, src, *in, Cin)) {
+    pdr::launch_fused_layer_ws(pp.id, src, *in, Cin, Wt, ldw, bias, D, nullptr, 0, nullptr, D, nt, pp.ncol, s, false,
+                               &pa);
     return pdr::check_launch();
+  }
   // tile subsets / row maps / patched rows: wave-specialised kernels only
   if (in->tile_list || in->out_rows || in->patch_values) return PDR_EUNSUPPORTED;
-#define PDR_LAUNCH_P(RT, CT, WR, WC, KC)                                                              \
-  hipLaunchKernelGGL((fused_layer_kernel<RT, CT, WR, WC, KC, false, true, false, true>), grid, dim3(256), \
-                     0, s, *in, Cin, Wt, ldw, bias, D, static_cast<float*>(nullptr), 0,                   \
-                     static_cast<float*>(nullptr), D, nt, pa)
-  switch (t.id) {
-    case 0: PDR_LAUNCH_P(2, 1, 4, 1, 16); break;
-    case 1: PDR_LAUNCH_P(2, 2, 4, 1, 16); break;
-    case 2: PDR_LAUNCH_P(1, 3, 4, 1, 32); break;
-    case 3: PDR_LAUNCH_P(1, 5, 4, 1, 32); break;
-    case 4: PDR_LAUNCH_P(2, 2, 2, 2, 32); break;
-    case 5: PDR_LAUNCH_P(1, 2, 2, 2, 32); break;
-    case 7: PDR_LAUNCH_P(1, 1, 4, 1, 32); break;
-    case 8: PDR_LAUNCH_P(1, 2, 4, 1, 32); break;
-    default: PDR_LAUNCH_P(1, 1, 1, 4, 32); break;
-  }
-#undef PDR_LAUNCH_P
+  const LayerArgs a{s, *in, Cin, Wt, ldw, bias, D, nullptr, 0, nullptr, D, nt, pa};
+  pdr::with_tile(pp.id, [&](auto t) { launch_k<decltype(t), false, true, false, true>(uniform_grid(pp.ntiles, pp.ncol), a); });
   return pdr::check_launch();
 }
 

@@ -23,7 +23,7 @@
 // Results equal fused_layer_kernel up to fp32 summation order (the bias is the accumulators' initial value here).
 #include <cstdlib>
 
-#include "pdr_common.h"
+#include "layer_tiles.h"
 
 #include <type_traits>
 
@@ -1070,18 +1070,17 @@ extern "C" int pdr_lab_trace_read(unsigned long long* dst) {
 namespace pdr {
 
 // Whether tile variant `id` (pick_tile() of fused_layer.hip) has a wave-specialised instantiation for this input.
-bool fused_layer_ws_supported(int id, bool radd, bool gath, const pdr_layer_in_t& in, int Cin) {
+bool fused_layer_ws_supported(int id, const LayerSource& src, const pdr_layer_in_t& in, int Cin) {
+  const bool radd = src.radd, gath = src.gath, knn = src.knn, knn_res = src.knn_res;
   if (Cin > kMaxCin) return false;   // identity scale / shift / add arrays cover kMaxCin channels
   if (in.wrow0 && gath) return false;   // weighted statistics: the plain-source instantiations (and the uniform kernel)
+  if (id < 0 || id >= kNumTiles) return false;
   // a row map of the per-query term: gathered instantiations read it per 32-row block only (one query per block), on
-  // full row tiles only (their per-row path of a partial last tile has no row map) -- whole tiles of the variant: 256
-  // rows for 0 / 1, 128 for the rest (variant 5's 64-row tiles included: such calls stay on the uniform-wave kernel)
-  const int tm_map = id <= 1 ? 256 : 128;
+  // full row tiles only (their per-row path of a partial last tile has no row map) -- whole tiles of the variant, and
+  // no fewer than 128 rows (variant 5's 64-row tiles: such calls stay on the uniform-wave kernel)
+  const int tm_map = tile_tm(id) > 128 ? tile_tm(id) : 128;
   if (in.oadd_rows && gath && (in.oadd_div < 32 || in.rows_per_batch % tm_map != 0)) return false;
-  if (id == 3 || id == 6 || id > 8) return false;   // 128 x 160 (80 accumulators) and 32-row tiles: uniform-wave kernel
-  bool knn = false;
-  for (int sg = 0; sg < in.n_seg; ++sg) knn = knn || in.seg[sg].g_r1 != nullptr;
-  const bool knn_res = in.rseg.gV && in.rseg.g_r1;
+  if (!tile_has_ws(id)) return false;   // 128 x 160 (80 accumulators) and 32-row tiles: uniform-wave kernel
   if (in.oadd_rows && (knn || knn_res)) return false;   // (no row map in the kNN-form instantiations)
   if (knn) {
     // kNN-form gathered sources: both per-position arrays, both rows on every gathered segment, no empty balls
@@ -1112,24 +1111,48 @@ bool fused_layer_ws_supported(int id, bool radd, bool gath, const pdr_layer_in_t
   return true;
 }
 
-// Launches the wave-specialised kernel for tile variant `id`.  Returns false when the variant has no
-// wave-specialised instantiation.  split: f16x3 arithmetic (Wt = packed weight image, ldw = chunks per column
-// block); instantiated for the 128-column tile variants 4 and 5 and the 64-column variant 8.
-bool launch_fused_layer_ws(int id, bool radd, bool gath, const pdr_layer_in_t& in, int Cin, const float* Wt,
-                           int ldw, const float* bias, int Cout, float* Y, int ldy, float* partial,
-                           int relu_col0, int n_row_tiles, int ncol, hipStream_t s, bool split, const PoolArgs* pool) {
-  if (!fused_layer_ws_supported(id, radd, gath, in, Cin)) return false;
-  if (split && id != 4 && id != 5 && id != 8) return false;
-  if (pool && (radd || gath || in.oadd)) return false;   // pooled epilogue: plain sources
-  const PoolArgs pa = pool ? *pool : PoolArgs();
-  // persistent: at most 2 workgroups per CU, all co-resident
-  long gx = n_row_tiles;
+}  // namespace pdr
+
+namespace {
+
+// everything of a wave-specialised launch but the template arguments
+struct WsArgs {
+  dim3 grid; hipStream_t s; const pdr_layer_in_t& in; int Cin; const float* Wt; int ldw; const float* bias; int Cout;
+  float* Y; int ldy; float* partial; int relu_col0, n_row_tiles, tile_order; pdr::PoolArgs pool; pdr::WsTwin twin;
+};
+
+template <class T, bool RADD, int GATH, bool SPLIT, bool POOL = false, bool PAIR = false>
+void ws_launch(const WsArgs& a) {
+  hipLaunchKernelGGL((fused_layer_ws_kernel<T::RT, T::CT, T::WR, T::WC, T::KC, RADD, GATH, SPLIT, POOL, PAIR>), a.grid,
+                     dim3(512), 0, a.s, a.in, a.Cin, a.Wt, a.ldw, a.bias, a.Cout, a.Y, a.ldy, a.partial, a.relu_col0,
+                     a.n_row_tiles, a.tile_order, a.pool, a.twin);
+}
+
+// the source form of an unpooled launch: residual x (plain / ball-gathered / kNN-gathered)
+template <class T, bool SPLIT>
+void ws_launch_form(const WsArgs& a, const pdr::LayerSource& src) {
+  if (src.gath && src.knn) ws_launch<T, false, 2, SPLIT>(a);
+  else if (src.gath && src.radd && src.knn_res) ws_launch<T, true, 2, SPLIT>(a);
+  else if (src.gath && src.radd) ws_launch<T, true, 1, SPLIT>(a);
+  else if (src.gath) ws_launch<T, false, 1, SPLIT>(a);
+  else if (src.radd) ws_launch<T, true, 0, SPLIT>(a);
+  else ws_launch<T, false, 0, SPLIT>(a);
+}
+
+}  // namespace
+
+namespace pdr {
+
+void launch_fused_layer_ws(int id, const LayerSource& src, const pdr_layer_in_t& in, int Cin, const float* Wt, int ldw,
+                           const float* bias, int Cout, float* Y, int ldy, float* partial, int relu_col0,
+                           int n_row_tiles, int ncol, hipStream_t s, bool split, const PoolArgs* pool) {
   // persistent: every workgroup co-resident -- 2 per CU, 3 for the narrow tiles without a residual (see above);
   // option ws_narrow3 = 0: 2 for all (A/B)
+  long gx = n_row_tiles;
   const bool narrow3 = pdr::option(pdr::OPT_WS_NARROW3) != 0;
   // (launching only half of the co-resident workgroups, so that the kernels of the two block-half streams share every
   // CU instead of taking turns, measured 9.51 / 9.58 vs 8.78 / 8.79 ms per step in round 3 -- removed)
-  const long resident = (narrow3 && id == 7 && !radd && !split) ? 768 : 512;
+  const long resident = (narrow3 && id == 7 && !src.radd && !split) ? 768 : 512;
   // Option ws_xcd_order: 1 (default) = XCD-local cloud-major tile order for the gathered kernels, 2 = for every layer,
   // 0 = plain.  Measured (same box, B = 32): HBM traffic of the kNN-gathered wide tiles 213.7 -> 170.5 MB per launch
   // (143 MB algorithmic), of the kNN-gathered narrow tiles 178 -> 143 MB, ball-gathered kernels unchanged; step time
@@ -1139,7 +1162,7 @@ bool launch_fused_layer_ws(int id, bool radd, bool gath, const pdr_layer_in_t& i
   // time (the kernels are MFMA-bound), which is why the gathered kernels take it by default and the others do not.
   // Results are bit-identical (tools/lab/order_check.py, tests).
   const int xcd_knob = pdr::option(pdr::OPT_WS_XCD_ORDER);
-  const int tile_order = (xcd_knob >= 2 || (xcd_knob == 1 && gath)) ? 1 : 0;
+  const int tile_order = (xcd_knob >= 2 || (xcd_knob == 1 && src.gath)) ? 1 : 0;
   long cap = (resident + ncol - 1) / ncol;
   // (whole groups of 8 workgroups for the XCD-local walk; fewer than 8 resident column-block workgroups -- ncol > 64
   // -- keep the plain walk instead of rounding the grid down to nothing)
@@ -1148,93 +1171,29 @@ bool launch_fused_layer_ws(int id, bool radd, bool gath, const pdr_layer_in_t& i
   else tile_order_eff = 0;
   if (gx > cap) gx = cap;
   if (gx < 1) gx = 1;
-  const dim3 grid(static_cast<unsigned>(gx), static_cast<unsigned>(ncol));
-#define PDR_WS_K(RT, CT, WR, WC, KC, RA, GA, SP)                                                          \
-  hipLaunchKernelGGL((fused_layer_ws_kernel<RT, CT, WR, WC, KC, RA, GA, SP>), grid, dim3(512), 0, s, in, \
-                     Cin, Wt, ldw, bias, Cout, Y, ldy, partial, relu_col0, n_row_tiles, tile_order_eff, pa, pdr::WsTwin())
-#define PDR_WS_POOL(RT, CT, WR, WC, KC)                                                                       \
-  hipLaunchKernelGGL((fused_layer_ws_kernel<RT, CT, WR, WC, KC, false, 0, false, true>), grid, dim3(512), 0, s, \
-                     in, Cin, Wt, ldw, bias, Cout, Y, ldy, partial, relu_col0, n_row_tiles, tile_order_eff, pa, pdr::WsTwin())
-  bool knn = false;
-  for (int sg = 0; sg < in.n_seg; ++sg) knn = knn || in.seg[sg].g_r1 != nullptr;
-  const bool knn_res = in.rseg.gV && in.rseg.g_r1;
-#define PDR_WS(RT, CT, WR, WC, KC)                            \
-  do {                                                        \
-    if (gath && knn) PDR_WS_K(RT, CT, WR, WC, KC, false, 2, false); \
-    else if (gath && radd && knn_res) PDR_WS_K(RT, CT, WR, WC, KC, true, 2, false);  \
-    else if (gath && radd) PDR_WS_K(RT, CT, WR, WC, KC, true, 1, false);  \
-    else if (gath) PDR_WS_K(RT, CT, WR, WC, KC, false, 1, false);  \
-    else if (radd) PDR_WS_K(RT, CT, WR, WC, KC, true, 0, false); \
-    else PDR_WS_K(RT, CT, WR, WC, KC, false, 0, false);       \
-  } while (0)
-#define PDR_WS_SPLIT(RT, CT, WR, WC, KC)                      \
-  do {                                                        \
-    if (gath && knn) PDR_WS_K(RT, CT, WR, WC, KC, false, 2, true); \
-    else if (gath && radd && knn_res) PDR_WS_K(RT, CT, WR, WC, KC, true, 2, true);   \
-    else if (gath && radd) PDR_WS_K(RT, CT, WR, WC, KC, true, 1, true);   \
-    else if (gath) PDR_WS_K(RT, CT, WR, WC, KC, false, 1, true);   \
-    else if (radd) PDR_WS_K(RT, CT, WR, WC, KC, true, 0, true); \
-    else PDR_WS_K(RT, CT, WR, WC, KC, false, 0, true);        \
-  } while (0)
-  if (pool && split) {
-#define PDR_WS_POOL_SPLIT(RT, CT, WR, WC, KC)                                                                  \
-  hipLaunchKernelGGL((fused_layer_ws_kernel<RT, CT, WR, WC, KC, false, 0, true, true>), grid, dim3(512), 0, s, \
-                     in, Cin, Wt, ldw, bias, Cout, Y, ldy, partial, relu_col0, n_row_tiles, tile_order_eff, pa, pdr::WsTwin())
-    if (id == 4) PDR_WS_POOL_SPLIT(2, 2, 2, 2, 32);
-    else if (id == 5) PDR_WS_POOL_SPLIT(1, 2, 2, 2, 32);
-    else PDR_WS_POOL_SPLIT(1, 2, 4, 1, 32);
-#undef PDR_WS_POOL_SPLIT
-    return true;
-  }
-  if (pool) {
-    switch (id) {
-      case 0: PDR_WS_POOL(2, 1, 4, 1, 16); return true;
-      case 1: PDR_WS_POOL(2, 2, 4, 1, 16); return true;
-      case 2: PDR_WS_POOL(1, 3, 4, 1, 32); return true;
-      case 4: PDR_WS_POOL(2, 2, 2, 2, 32); return true;
-      case 5: PDR_WS_POOL(1, 2, 2, 2, 32); return true;
-      case 7: PDR_WS_POOL(1, 1, 4, 1, 32); return true;
-      case 8: PDR_WS_POOL(1, 2, 4, 1, 32); return true;
-      default: return false;
+  const WsArgs a{dim3(static_cast<unsigned>(gx), static_cast<unsigned>(ncol)), s, in, Cin, Wt, ldw, bias, Cout, Y, ldy,
+                 partial, relu_col0, n_row_tiles, tile_order_eff, pool ? *pool : PoolArgs(), WsTwin()};
+  with_tile(id, [&](auto t) {
+    using T = decltype(t);
+    if constexpr (tile_has_ws(T::id)) {
+      if constexpr (tile_has_split(T::id)) {
+        if (split) {
+          if (pool) ws_launch<T, false, 0, true, true>(a);
+          else ws_launch_form<T, true>(a, src);
+          return;
+        }
+      }
+      if (pool) ws_launch<T, false, 0, false, true>(a);   // pooled epilogue: plain sources
+      else ws_launch_form<T, false>(a, src);
     }
-  }
-  if (split) {
-    if (id == 4) PDR_WS_SPLIT(2, 2, 2, 2, 32);
-    else if (id == 5) PDR_WS_SPLIT(1, 2, 2, 2, 32);
-    else PDR_WS_SPLIT(1, 2, 4, 1, 32);
-    return true;
-  }
-  switch (id) {
-    case 0: PDR_WS(2, 1, 4, 1, 16); return true;
-    case 1: PDR_WS(2, 2, 4, 1, 16); return true;
-    case 2: PDR_WS(1, 3, 4, 1, 32); return true;
-    // case 3 (128 x 160: 80 accumulators) does not fit the 128-register budget: uniform-wave kernel
-    case 4: PDR_WS(2, 2, 2, 2, 32); return true;
-    case 5: PDR_WS(1, 2, 2, 2, 32); return true;
-    case 7: PDR_WS(1, 1, 4, 1, 32); return true;
-    case 8: PDR_WS(1, 2, 4, 1, 32); return true;
-    default: return false;
-  }
-#undef PDR_WS
-#undef PDR_WS_SPLIT
-#undef PDR_WS_K
-#undef PDR_WS_POOL
+  });
 }
 
 // One launch for two problems of the same layer (see PAIR above).  Grid: the first problem's persistent workgroups (as
 // launch_fused_layer_ws would size them) followed by the second's.
-bool launch_fused_layer_ws_pair(int id, bool gath, const pdr_layer_in_t& in, int Cin, const float* Wt, int ldw,
+void launch_fused_layer_ws_pair(int id, bool gath, const pdr_layer_in_t& in, int Cin, const float* Wt, int ldw,
                                 const float* bias, int Cout, float* Y, int ldy, float* partial, int relu_col0,
                                 int n_row_tiles, int ncol, WsTwin twin, hipStream_t s) {
-  if (!(id == 2 || id == 4 || id == 7 || id == 8)) return false;                 // 128-row tiles
-  if (!fused_layer_ws_supported(id, false, gath, in, Cin)) return false;
-  const pdr_layer_in_t& in2 = twin.in[1];
-  if (!fused_layer_ws_supported(id, false, false, in2, Cin)) return false;
-  bool knn = false;
-  for (int sg = 0; sg < in.n_seg; ++sg) knn = knn || in.seg[sg].g_r1 != nullptr;
-  if (knn || in.rseg.ptr || in2.rseg.ptr || in2.tile_list || in2.gidx) return false;
-  for (int sg = 0; sg < in2.n_seg; ++sg)
-    if (in2.seg[sg].gV) return false;
   const long resident = 512;
   long cap = (resident + ncol - 1) / ncol;
   long gx1 = n_row_tiles < cap ? n_row_tiles : cap;
@@ -1247,25 +1206,15 @@ bool launch_fused_layer_ws_pair(int id, bool gath, const pdr_layer_in_t& in, int
   twin.partial[0] = partial;
   twin.ldy[0] = ldy;
   twin.n_row_tiles[0] = n_row_tiles;
-  const dim3 grid(static_cast<unsigned>(gx1 + gx2), static_cast<unsigned>(ncol));
-  const PoolArgs pa = PoolArgs();
-#define PDR_WS_PAIR(RT, CT, WR, WC, KC)                                                                              \
-  do {                                                                                                               \
-    if (gath)                                                                                                        \
-      hipLaunchKernelGGL((fused_layer_ws_kernel<RT, CT, WR, WC, KC, false, 1, false, false, true>), grid, dim3(512), \
-                         0, s, in, Cin, Wt, ldw, bias, Cout, Y, ldy, partial, relu_col0, n_row_tiles, 0, pa, twin);  \
-    else                                                                                                             \
-      hipLaunchKernelGGL((fused_layer_ws_kernel<RT, CT, WR, WC, KC, false, 0, false, false, true>), grid, dim3(512), \
-                         0, s, in, Cin, Wt, ldw, bias, Cout, Y, ldy, partial, relu_col0, n_row_tiles, 0, pa, twin);  \
-  } while (0)
-  switch (id) {
-    case 2: PDR_WS_PAIR(1, 3, 4, 1, 32); return true;
-    case 4: PDR_WS_PAIR(2, 2, 2, 2, 32); return true;
-    case 7: PDR_WS_PAIR(1, 1, 4, 1, 32); return true;
-    case 8: PDR_WS_PAIR(1, 2, 4, 1, 32); return true;
-    default: return false;
-  }
-#undef PDR_WS_PAIR
+  const WsArgs a{dim3(static_cast<unsigned>(gx1 + gx2), static_cast<unsigned>(ncol)), s, in, Cin, Wt, ldw, bias, Cout,
+                 Y, ldy, partial, relu_col0, n_row_tiles, 0, PoolArgs(), twin};
+  with_tile(id, [&](auto t) {
+    using T = decltype(t);
+    if constexpr (tile_has_pair(T::id)) {
+      if (gath) ws_launch<T, false, 1, false, false, true>(a);
+      else ws_launch<T, false, 0, false, false, true>(a);
+    }
+  });
 }
 
 }  // namespace pdr

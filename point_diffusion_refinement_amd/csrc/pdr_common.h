@@ -73,18 +73,6 @@ struct WsTwin {
   int gx;               // workgroups (grid.x) of the first problem; 0 = not a paired launch
 };
 
-// fused_layer_ws.hip: wave-specialised layer kernel; false = no instantiation for this tile variant
-bool fused_layer_ws_supported(int variant, bool radd, bool gath, const pdr_layer_in_t& in, int Cin);
-bool launch_fused_layer_ws(int variant, bool radd, bool gath, const pdr_layer_in_t& in, int Cin,
-                           const float* Wt, int ldw, const float* bias, int Cout, float* Y, int ldy,
-                           float* partial, int relu_col0, int n_row_tiles, int ncol, hipStream_t s,
-                           bool split = false, const PoolArgs* pool = nullptr);
-// one launch for (in, Y, partial) and (twin.in, twin.Y, twin.partial): plain or ball-gathered sources without a residual
-// in the first problem, plain sources in the second; false = no paired instantiation for this tile variant
-bool launch_fused_layer_ws_pair(int variant, bool gath, const pdr_layer_in_t& in, int Cin, const float* Wt, int ldw,
-                                const float* bias, int Cout, float* Y, int ldy, float* partial, int relu_col0,
-                                int n_row_tiles, int ncol, WsTwin twin, hipStream_t s);
-
 // ---- DPP wave reductions (wave64, gfx9 row_shr / row_bcast) -------------------
 // After wave_max_*: lane 63 holds the maximum; callers broadcast with readlane.
 template <int CTRL>

@@ -394,7 +394,8 @@ def reference_stats(L, Y):
 
 
 # ---- generators --------------------------------------------------------------------------------------------------
-# tile rows of each variant (pick_tile of csrc/fused_layer.hip) and a Cout range that selects it
+# tile rows of each variant -- a copy of tile_tm() over pdr::kTiles (csrc/layer_tiles.h, the one table; Python cannot
+# include it) -- and a Cout range that makes pick_tile (csrc/fused_layer.hip) select it
 TILE_ROWS = {0: 256, 1: 256, 2: 128, 3: 128, 4: 128, 5: 64, 6: 32, 7: 128, 8: 128}
 COUTS = {0: (3, 32), 1: (33, 64), 2: (65, 96), 3: (129, 160), 4: (97, 128, 161), 5: (3, 33, 129, 161),
          6: (3, 65, 161), 7: (3, 32), 8: (33, 64)}
@@ -598,6 +599,46 @@ def random_cases(opt, n, seed=0):
                  bias=bool(rng.integers(0, 4)), stats=bool(rng.integers(0, 5)))
         out.append(Case(B=B, rpb=rpb, segs=segs, Cout=Cout, form=form, K=K, div=div, seed=10000 + i,
                         tag="%s random %d" % (opt, i), **f))
+    return out
+
+
+def corner_cases():
+    """Malformed kNN marks, where the library's two readings of "kNN-form" differ (pdr::LayerSource, csrc/layer_tiles.h):
+    the kernel form follows g_r1 alone, the plan's refusal and its out[3] follow g_r1 OR g_r2.  Plan-level only (fake
+    addresses).  Each entry: (label, options, Layer, expected rc, expected (out[0], out[2], out[3]) or None) -- what
+    the library returned before the dispatch had one source of truth, pinned so that it stays."""
+    OK, EUNSUP = _lib.PDR_OK, _lib.PDR_EUNSUPPORTED
+    row = 0x7000                                  # a fake (C,) row address
+
+    def layer(form, **marks):
+        L = build(Case(B=2, rpb=2048, segs=(64,), Cout=64, form=form, K=8), None)
+        for k, v in marks.items():
+            where, field = k.split("__")
+            setattr(L.li.seg[0] if where == "seg" else L.li.rseg, field, v)
+        return L
+
+    out = []
+    for ws in (1, 0):
+        o = {} if ws else {"fused_ws": 0}
+        t = "" if ws else " fused_ws=0"
+
+        def add(label, L, rc_ws, cell):
+            # without the wave-specialised kernels every marked call is refused
+            out.append((label + t, o, L, rc_ws if ws else EUNSUP, cell if ws and rc_ws == OK else None))
+        # g_r2 without g_r1: runs as the plain / ball form of the wave-specialised kernel; reported as kNN when gathered
+        add("plain + seg g_r2", layer("plain", seg__g_r2=row), OK, (1, 0, 0))
+        add("ball + seg g_r2", layer("ball", seg__g_r2=row), OK, (1, 0, 2))
+        add("ball_res + rseg g_r2", layer("ball_res", rseg__g_r2=row), OK, (1, 1, 2))
+        add("residual + seg g_r2", layer("residual", seg__g_r2=row), OK, (1, 1, 0))
+        # g_r1 alone is a kNN form without its arrays: no instantiation
+        add("plain + seg g_r1", layer("plain", seg__g_r1=row), EUNSUP, None)
+        add("ball + seg g_r1", layer("ball", seg__g_r1=row), EUNSUP, None)
+        add("ball_res + rseg g_r1", layer("ball_res", rseg__g_r1=row), EUNSUP, None)
+        # a stale gathered residual descriptor (rseg.gV without rseg.ptr) still carries its marks
+        add("plain + stale rseg gV g_r1", layer("plain", rseg__gV=row, rseg__g_r1=row), EUNSUP, None)
+        add("plain + stale rseg gV g_r2", layer("plain", rseg__gV=row, rseg__g_r2=row), OK, (1, 0, 0))
+    # an unmarked stale descriptor is ignored either way
+    out.append(("plain + stale rseg gV fused_ws=0", {"fused_ws": 0}, layer("plain", rseg__gV=row), OK, (0, 0, 0)))
     return out
 
 

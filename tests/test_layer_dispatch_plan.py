@@ -77,6 +77,19 @@ def test_plan_reaches_every_dispatch_cell_and_refuses_what_the_launch_refuses():
     assert not no_partial, "cells never reached with a partial last tile: %s" % no_partial
 
 
+def test_plan_keeps_the_malformed_knn_mark_corners():
+    """g_r2 without g_r1 (and a gathered residual descriptor without its residual pointer): the kernel form and the
+    plan's refusal read the kNN marks differently; the merged rule returns what the separate copies returned."""
+    corners = lc.corner_cases()
+    assert len(corners) == 19
+    for label, opts, L, want_rc, want in corners:
+        with lc.options(opts):
+            rc, out = L.plan()
+        assert rc == want_rc, (label, rc, out)
+        if want is not None:
+            assert (out[0], out[2], out[3]) == want, (label, out)
+
+
 def test_advisor_case_leaves_the_wave_specialised_kernel():
     """narrow_kc32 = 0, 384 rows per cloud (a 256-row tile and a half tile), ball-gathered source, per-query term
     through a row map: the gathered wave-specialised instantiations have no row map on a partial tile, so the call

@@ -30,7 +30,8 @@ F16_MFMA_PEAK_TFLOPS = 2500.0
 HBM_PEAK_GBS = 8000.0
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
-# tile variants of pdr_fused_layer (csrc/fused_layer.hip pick_tile / launch tables): id -> <RT, CT, WR, WC, KC>
+# tile variants of pdr_fused_layer, id -> <RT, CT, WR, WC, KC>: a copy of pdr::kTiles (csrc/layer_tiles.h, the one
+# table every launch site is derived from; Python cannot include it) -- keep the two in step
 _VARIANT = {0: (2, 1, 4, 1, 16), 1: (2, 2, 4, 1, 16), 2: (1, 3, 4, 1, 32), 3: (1, 5, 4, 1, 32), 4: (2, 2, 2, 2, 32),
             5: (1, 2, 2, 2, 32), 6: (1, 1, 1, 4, 32), 7: (1, 1, 4, 1, 32), 8: (1, 2, 4, 1, 32)}
 

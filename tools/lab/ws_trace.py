@@ -47,6 +47,7 @@ def main():
     print("chunk | consumer: wait  compute  epi | producer: loadwait  commit  fetch-issue | c.period | p.arrive-c.arrive")
     e = buf[2].reshape(-1, 8).astype(np.int64)
     rpb, Cin, Cout = FB.SHAPES[idx]
+    # channels per chunk of the variant: a copy of the KC column of pdr::kTiles (csrc/layer_tiles.h, the one table)
     kc = 16 if (lib.pdr_fused_layer_variant(rpb, Cout) in (0, 1)) else 32
     nch = (Cin + kc - 1) // kc
     print("epilogue checkpoints per tile (ticks after the last MFMA issue; slot 0: end of column tile 0, 1: Tt writes of "
