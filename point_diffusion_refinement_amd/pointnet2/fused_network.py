@@ -29,6 +29,7 @@ grouped block is split into per-point tables (SplitFirstConv), and a neighbourho
 128-row tiles that hold a real neighbourhood, a per-query chain of the same layers stands in for the rest).
 """
 import ctypes
+from collections import namedtuple
 
 import torch
 import torch.nn as nn
@@ -209,31 +210,51 @@ def _ptr(t, offset=0):
     return t.data_ptr() + 4 * offset
 
 
-def _fill_seg(cseg, seg):
-    """seg = (tensor, offset_floats, C, ld, row_div[, gather]) -> pdr_seg_t."""
-    t, off, C, ld, div = seg[:5]
-    cseg.ptr, cseg.C, cseg.ld, cseg.row_div = _ptr(t, off), C, ld, div
-    g = seg[5] if len(seg) > 5 else None
-    if g is not None:
-        cseg.gV = _ptr(g["V"][0], g["V"][1])
-        cseg.gV0 = _ptr(g["V0"][0], g["V0"][1]) if g.get("V0") is not None else None
-        cseg.g_ldv, cseg.g_nsrc = g["ldv"], g["nsrc"]
-        cseg.g_zrow = g.get("zrow", -1)
-        if g.get("r1") is not None:                     # kNN form: + s1[p] r1[c] + s2[p] r2[c]
-            cseg.g_r1, cseg.g_r2 = _ptr(g["r1"][0], g["r1"][1]), _ptr(g["r2"][0], g["r2"][1])
+# The gathered form of a source segment: row p reads U[gidx[p]] + V[p / gK] (V0 for an empty ball; kNN form:
+# + gs1[p] r1 + gs2[p] r2).  V / V0 / r1 / r2 are (tensor, offset in floats) pairs.
+Gather = namedtuple("Gather", "V V0 ldv nsrc zrow r1 r2", defaults=(-1, None, None))
+
+
+class Seg(namedtuple("Seg", "t off C ld div gather", defaults=(1, None))):
+    """One source segment of an Act: columns [off, off + C) of the (rows, ld) tensor `t`; row p reads row p / div;
+    `gather`: `t` is a per-source-point table read through the Act's neighbour index (a Gather)."""
+    __slots__ = ()
+
+    @property
+    def gathered(self):
+        return self.gather is not None
+
+    @staticmethod
+    def of(s):
+        """A Seg from what call sites may hand over: a Seg, or its fields as a plain tuple (gather part as a dict)."""
+        s = s if isinstance(s, Seg) else Seg(*s)
+        return s._replace(gather=Gather(**s.gather)) if isinstance(s.gather, dict) else s
+
+    def fill(self, cseg):
+        """-> pdr_seg_t."""
+        cseg.ptr, cseg.C, cseg.ld, cseg.row_div = _ptr(self.t, self.off), self.C, self.ld, self.div
+        g = self.gather
+        if g is not None:
+            cseg.gV = _ptr(*g.V)
+            cseg.gV0 = _ptr(*g.V0) if g.V0 is not None else None
+            cseg.g_ldv, cseg.g_nsrc, cseg.g_zrow = g.ldv, g.nsrc, g.zrow
+            if g.r1 is not None:                            # kNN form: + s1[p] r1[c] + s2[p] r2[c]
+                cseg.g_r1, cseg.g_r2 = _ptr(*g.r1), _ptr(*g.r2)
 
 
 class Act:
-    """A lazily-evaluated activation: channel segments + the prologue the consumer applies."""
+    """A lazily-evaluated activation: channel segments (`segs`, a list of Seg; `radd`, one Seg covering all channels
+    that is added row-wise) + the prologue the consumer applies.  Segments may be given as Seg or as plain tuples
+    (tensor, offset_floats, C, ld[, row_div[, gather as Gather or dict]]); they are Seg from here on."""
 
     def __init__(self, segs, P, B, rows_per_batch, scale=None, shift=None, add=None, add_ld=0, radd=None,
                  pre_relu=False, post_relu=False):
-        self.segs = segs          # [(tensor, offset_floats, C, ld, row_div[, gather dict])]
+        self.segs = [Seg.of(s) for s in segs]
         self.P, self.B, self.rpb = P, B, rows_per_batch
         self.scale, self.shift, self.add, self.add_ld = scale, shift, add, add_ld
-        self.radd = radd          # a segment tuple covering all channels, or None
+        self.radd = None if radd is None else Seg.of(radd)
         self.pre_relu, self.post_relu = pre_relu, post_relu
-        self.C = sum(s[2] for s in segs)
+        self.C = sum(s.C for s in self.segs)
         self.gidx = self.gcnt = None   # shared neighbour index / ball counts of gathered segments
         self.gK = 0
         self.gs1 = self.gs2 = None     # kNN form: per-position distance / weight of gathered segments
@@ -244,7 +265,6 @@ class Act:
         self.dd = None                 # Dedup plan of the block: the launch walks its tile subset
         self.twin = None               # the same activation over the block's per-QUERY rows (first neighbour only)
         self.wrow0, self.wmul = None, 0.0   # a twin's weighted statistics: rows >= wrow0[b] count, x wmul
-        self.ptpb = 0                  # partial rows per cloud of the launch in flight (run_layer sets it)
         self.patch = None              # pooled launch: (per-query value rows, row weights) of the skipped tiles
 
     def walk(self):
@@ -253,12 +273,12 @@ class Act:
         if not ZIGZAG_WALK or self.dd is not None:
             return 0
         best = None
-        for sg in list(self.segs) + ([self.radd] if self.radd is not None else []):
-            if (len(sg) <= 5 or sg[5] is None) and sg[4] == 1 and (best is None or sg[2] > best[2]):
+        for sg in self.segs + ([self.radd] if self.radd is not None else []):
+            if not sg.gathered and sg.div == 1 and (best is None or sg.C > best.C):
                 best = sg
         if best is None:
             return 0
-        return 1 - _WALK.get(best[0].data_ptr(), 1)
+        return 1 - _WALK.get(best.t.data_ptr(), 1)
 
     _SHARED = ("scale", "shift", "add", "add_ld", "pre_relu", "post_relu", "ss_ld")
 
@@ -268,17 +288,19 @@ class Act:
         if tw is not None and k in Act._SHARED:            # the prologue is the same for both row sets
             object.__setattr__(tw, k, v)
 
-    def struct(self):
+    def struct(self, partial_tpb=0, weighted=True):
+        """-> pdr_layer_in_t.  partial_tpb: rows per cloud of the statistics tensor the launch writes (0: the tile
+        subset's own count, or one row per tile); weighted=False: a twin's launch without its weighted statistics."""
         li = _lib.LayerIn()
         li.n_seg = len(self.segs)
         for i, seg in enumerate(self.segs):
-            _fill_seg(li.seg[i], seg)
+            seg.fill(li.seg[i])
         li.scale = self.scale.data_ptr() if self.scale is not None else None
         li.shift = self.shift.data_ptr() if self.shift is not None else None
         li.add = self.add.data_ptr() if self.add is not None else None
         li.add_ld = self.add_ld if self.add is not None else 0
         if self.radd is not None:
-            _fill_seg(li.rseg, self.radd)
+            self.radd.fill(li.rseg)
         li.pre_relu, li.post_relu, li.rows_per_batch = int(self.pre_relu), int(self.post_relu), self.rpb
         li.ss_ld = self.ss_ld
         if self.oadd is not None:
@@ -291,12 +313,11 @@ class Act:
             li.gK = self.gK
             if self.gs1 is not None:
                 li.gs1, li.gs2 = self.gs1.data_ptr(), self.gs2.data_ptr()
+        li.partial_tpb = partial_tpb
         if self.dd is not None:
             li.tile_list, li.n_tiles = self.dd.tile_list.data_ptr(), self.dd.n_tiles.data_ptr()
-            li.partial_tpb = self.ptpb or self.dd.ptpb
-        elif self.ptpb:
-            li.partial_tpb = self.ptpb
-        if self.wrow0 is not None:
+            li.partial_tpb = partial_tpb or self.dd.ptpb
+        if weighted and self.wrow0 is not None:
             li.wrow0, li.wmul = self.wrow0.data_ptr(), self.wmul
         if self.patch is not None:
             Vd, w = self.patch
@@ -404,28 +425,40 @@ class SortedQueries:
             self.plan = Dedup(self.idx, self.counts, B, m, K)
 
 
-class LayerOut(tuple):
-    """What run_layer returns: the tuple (Y, partial, tiles_per_batch[, (scale, shift)]) -- callers unpack it -- plus, as
-    explicit attributes, what a DEDUPLICATED layer adds: `twin` (the output of its per-query rows), `dd` (the block's
-    Dedup plan) and `sub` (which rows of `partial` hold something: (valid tiles per cloud, main tiles per cloud), the
-    subset arguments of pdr_gn_fold).  (Rounds 4-5 hung these on the tensors themselves -- `Y._twin`, `partial._sub` --,
-    where a `.view()` or `.contiguous()` would have dropped them without a word.)"""
+# Columns [col0, col0 + C) of a set of statistics, counted `mult` times: what Norm.fold and FoldReq.second take
+# (Stats.window makes one; a plain tuple of the same fields is accepted).
+Window = namedtuple("Window", "partial col0 C tpb mult sub", defaults=(1.0, None))
 
-    def __new__(cls, items, twin=None, dd=None, sub=None):
-        o = super().__new__(cls, items)
-        o.twin, o.dd, o.sub = twin, dd, sub
-        return o
+
+class Stats(namedtuple("Stats", "partial tpb sub", defaults=(None,))):
+    """The GroupNorm moments a launch wrote: `partial` (B tpb, C, 2) -- None when none were asked for --, its rows per
+    cloud `tpb`, and, when a tile subset produced them, `sub` = (valid tiles per cloud, main tiles per cloud), the
+    subset arguments of pdr_gn_fold."""
+    __slots__ = ()
+
+    def window(self, col0, C, mult=1.0):
+        return Window(self.partial, col0, C, self.tpb, mult, self.sub)
+
+
+class LayerOut:
+    """What run_layer returns: `Y`, its `stats` (a Stats), `folded` = (scale, shift) when a fold was requested with the
+    layer, and what a DEDUPLICATED layer adds: `twin` (the output of its per-query rows) and `dd` (the block's Dedup
+    plan).  Iterating gives (Y, partial, tiles_per_batch), the spelling of the kernel tests."""
+    __slots__ = ("Y", "stats", "folded", "twin", "dd")
+
+    def __init__(self, Y, stats, folded=None, twin=None, dd=None):
+        self.Y, self.stats, self.folded, self.twin, self.dd = Y, stats, folded, twin, dd
+
+    def __iter__(self):
+        return iter((self.Y, self.stats.partial, self.stats.tpb))
 
 
 def act_from(lo, C, P, B, rpb, **kw):
-    """Act over the first C columns of a layer output (a LayerOut, with its per-query twin when the layer ran
-    deduplicated, or a plain tensor)."""
-    Y = lo[0] if isinstance(lo, LayerOut) else lo
-    a = Act([(Y, 0, C, Y.shape[1], 1)], P, B, rpb, **kw)
-    dd = lo.dd if isinstance(lo, LayerOut) else None
-    if dd is not None:
-        a.dd = dd
-        a.twin = _twin_act([(lo.twin, 0, C, lo.twin.shape[1], 1)], dd, B, **kw)
+    """Act over the first C columns of a LayerOut, with its per-query twin when the layer ran deduplicated."""
+    a = Act([Seg(lo.Y, 0, C, lo.Y.shape[1])], P, B, rpb, **kw)
+    if lo.dd is not None:
+        a.dd = lo.dd
+        a.twin = _twin_act([Seg(lo.twin, 0, C, lo.twin.shape[1])], lo.dd, B, **kw)
     return a
 
 
@@ -438,20 +471,20 @@ def _twin_act(segs, dd, B, **kw):
 
 
 class FirstOut:
-    """Output of a block's first conv: a materialised (P, ld) tensor, or VIRTUAL = per-source-point table U
-    (with one all-zero row appended), per-query table V2 = [V | V0] and the neighbour index, read by consumers
-    as a gathered source.  In virtual form the residual columns [res_col0, res_col0 + res.shape... ) may still be
-    materialised (`Yres`): they are consumed as a row-wise residual, which stays a plain read."""
+    """Output of a block's first conv and its statistics (`stats`, a Stats): a materialised (P, ld) tensor, or VIRTUAL =
+    per-source-point table U (with one all-zero row appended), per-query table V2 = [V | V0] and the neighbour index,
+    read by consumers as a gathered source (seg() gives the Seg of a column window either way).  In virtual form the
+    residual columns [res_col0, res_col0 + res.shape... ) may still be materialised (`Yres`): they are consumed as a
+    row-wise residual, which stays a plain read."""
 
-    def __init__(self, Y=None, U=None, V2=None, ld=0, has_v0=False, idx=None, counts=None, K=0, nsrc=0, zrow=-1,
-                 Yres=None, res_col0=0, res_cols=0, s1=None, s2=None, r1=None, r2=None, materialise=None):
-        self.Y, self.U, self.V2, self.ld, self.has_v0 = Y, U, V2, ld, has_v0
+    def __init__(self, Y=None, stats=None, U=None, V2=None, ld=0, has_v0=False, idx=None, counts=None, K=0, nsrc=0,
+                 zrow=-1, Yres=None, res_col0=0, res_cols=0, s1=None, s2=None, r1=None, r2=None, materialise=None):
+        self.Y, self.stats, self.U, self.V2, self.ld, self.has_v0 = Y, stats, U, V2, ld, has_v0
         self.idx, self.counts, self.K, self.nsrc, self.zrow = idx, counts, K, nsrc, zrow
         self.Yres, self.res_col0, self.res_cols = Yres, res_col0, res_cols
         self.s1, self.s2, self.r1, self.r2 = s1, s2, r1, r2          # kNN form (r1 / r2: padded conv rows)
         self.materialise = materialise                                # (col0, C) -> (P, pad4(C)) tensor
         self.dd, self.deg = None, None      # Dedup plan + the first conv of the per-query rows (B m, ld), materialised
-        self.sub = None                     # the statistics came from a tile subset: (valid tiles per cloud, main tiles)
 
     @property
     def virtual(self):
@@ -459,14 +492,14 @@ class FirstOut:
 
     def seg(self, col0, C):
         if not self.virtual:
-            return (self.Y, col0, C, self.Y.shape[1], 1)
+            return Seg(self.Y, col0, C, self.Y.shape[1])
         if self.Yres is not None and col0 >= self.res_col0 and col0 + C <= self.res_col0 + self.res_cols:
-            return (self.Yres, col0 - self.res_col0, C, self.Yres.shape[1], 1)
-        g = {"V": (self.V2, col0), "V0": (self.V2, self.ld + col0) if self.has_v0 else None,
-             "ldv": self.V2.shape[1], "nsrc": self.nsrc, "zrow": self.zrow}
-        if self.s1 is not None:
-            g["r1"], g["r2"] = (self.r1, col0), (self.r2, col0)
-        return (self.U, col0, C, self.U.shape[1], 1, g)
+            return Seg(self.Yres, col0 - self.res_col0, C, self.Yres.shape[1])
+        kNN = self.s1 is not None
+        g = Gather(V=(self.V2, col0), V0=(self.V2, self.ld + col0) if self.has_v0 else None, ldv=self.V2.shape[1],
+                   nsrc=self.nsrc, zrow=self.zrow, r1=(self.r1, col0) if kNN else None,
+                   r2=(self.r2, col0) if kNN else None)
+        return Seg(self.U, col0, C, self.U.shape[1], 1, g)
 
     def attach(self, act):
         if self.virtual:
@@ -476,15 +509,15 @@ class FirstOut:
             dd, Yd = self.dd, self.deg
             if act.twin is None:
                 # the activation reads this first conv: its twin reads the same columns of the per-query rows
-                if len(act.segs) != 1 or len(act.segs[0]) <= 5:
+                if len(act.segs) != 1 or not act.segs[0].gathered:
                     raise NotImplementedError("deduplicated block: one gathered source per layer")
-                _, col0, C = act.segs[0][:3]
-                tw = _twin_act([(Yd, col0, C, Yd.shape[1], 1)], dd, act.B)
+                sg = act.segs[0]
+                tw = _twin_act([Seg(Yd, sg.off, sg.C, Yd.shape[1])], dd, act.B)
                 for k in Act._SHARED:
                     object.__setattr__(tw, k, getattr(act, k))
                 act.dd, act.twin = dd, tw
-            if act.radd is not None and len(act.radd) > 5:      # gathered residual window
-                act.twin.radd = (Yd, act.radd[1], act.radd[2], Yd.shape[1], 1)
+            if act.radd is not None and act.radd.gathered:      # gathered residual window
+                act.twin.radd = Seg(Yd, act.radd.off, act.radd.C, Yd.shape[1])
         return act
 
 
@@ -549,7 +582,7 @@ def plain(t2d, B, rows_per_batch, row_div=1, C=None):
     """Act over a (rows, ld) tensor whose first C columns are the channels (ld may be padded)."""
     rows, ld = t2d.shape
     C = ld if C is None else C
-    return Act([(t2d, 0, C, ld, row_div)], rows * row_div, B, rows_per_batch)
+    return Act([Seg(t2d, 0, C, ld, row_div)], rows * row_div, B, rows_per_batch)
 
 
 class Conv:
@@ -568,6 +601,15 @@ class Conv:
         self.bias = torch.cat([c.bias.detach() if c.bias is not None else torch.zeros(w.shape[0], device=dev)
                                for c, w in zip(convs, ws)]).contiguous()
         self.widths = [w.shape[0] for w in ws]
+        self.f16x3 = {}           # split-f16 weight images: source segment widths + (column-block width,) -> (image, chunks)
+        self.pair_ok = {}         # (rows per cloud, queries per cloud) -> False once pdr_fused_layer_pair declined the shape
+
+    def f16x3_image(self, seg_widths, TN):
+        """(image, chunks) of pack_f16x3 for sources of these widths and TN-column blocks, packed once."""
+        key = tuple(seg_widths) + (TN,)
+        if key not in self.f16x3:
+            self.f16x3[key] = pack_f16x3(self.Wt, self.Cout, key[:-1], TN)
+        return self.f16x3[key]
 
 
 # Every grouped block evaluates its two independent halves -- shared MLP + value conv | query conv + score convs --
@@ -596,7 +638,7 @@ FPS_STREAM = True
 _PAR = {"stream": None}
 
 
-def _ahead_on_aux(fn):
+def _on_aux(fn):
     """fn() on the blocks' second stream, behind everything the current stream has issued; returns a thunk that makes
     the current stream wait for it and yields fn's result (None when there is no second stream)."""
     aux = _PAR["stream"]
@@ -608,27 +650,6 @@ def _ahead_on_aux(fn):
     aux.wait_event(ev)
     with torch.cuda.stream(aux):
         result = fn()
-        done = torch.cuda.Event()
-        done.record(aux)
-
-    def join():
-        main.wait_event(done)
-        return result
-    return join
-
-
-def _fork_join(rows, chain_a):
-    """Run `chain_a()` on the auxiliary stream if this block qualifies; returns a thunk that joins and yields its
-    result (or the result itself when everything stays on the current stream)."""
-    aux = _PAR["stream"]
-    if aux is None:
-        return chain_a()
-    main = torch.cuda.current_stream()
-    fork = torch.cuda.Event()
-    fork.record(main)
-    aux.wait_event(fork)
-    with torch.cuda.stream(aux):
-        result = chain_a()
         done = torch.cuda.Event()
         done.record(aux)
 
@@ -698,7 +719,7 @@ def pack_f16x3(Wt, Cout, seg_widths, TN=128):
     return img.view(torch.int16).reshape(-1), len(chunks)
 
 
-def _run_layer_split(lib, act, conv, li, y_ptr, ldy, partial_ptr, relu_col0, tiny_exact=True):
+def _launch_split(lib, act, conv, li, y_ptr, ldy, partial_ptr, relu_col0, tiny_exact=True):
     """Try the f16x3 entry point; False when this layer is not carried by it (caller uses the exact kernel).
     tiny_exact=False: also for the tiny layers that run_layer leaves to the exact kernel (kernel tests)."""
     if _PRECISION[0] != "split_f16" or conv.Cin < SPLIT_MIN_CIN:
@@ -714,18 +735,16 @@ def _run_layer_split(lib, act, conv, li, y_ptr, ldy, partial_ptr, relu_col0, tin
     if lib.pdr_fused_layer_plan(ctypes.byref(li), act.P, conv.Cin, conv.Wt.data_ptr(), conv.ldw, conv.Cout, y_ptr, ldy,
                                 plan) == _lib.PDR_OK and plan[7] and tiny_exact:
         return False
-    TN = 64 if variant == 8 else 128
-    key = tuple(sg[2] for sg in act.segs) + (TN,)
-    cache = conv.__dict__.setdefault("_f16x3", {})
-    if key not in cache:
-        cache[key] = pack_f16x3(conv.Wt, conv.Cout, key[:-1], TN)
-    img, nch = cache[key]
+    img, nch = conv.f16x3_image([sg.C for sg in act.segs], 64 if variant == 8 else 128)
     rc = lib.pdr_fused_layer_f16x3(ctypes.byref(li), act.P, conv.Cin, img.data_ptr(), nch, conv.bias.data_ptr(),
                                     conv.Cout, y_ptr, ldy, partial_ptr, relu_col0, _stream())
     if rc == _lib.PDR_EUNSUPPORTED:
         return False
     _lib.check(rc, "fused_layer_f16x3")
     return True
+
+
+_run_layer_split = _launch_split          # (the name the kernel tests and tools/lab/split_half.py call it by)
 
 
 def _ldy(Cout):
@@ -737,7 +756,7 @@ def _ldy(Cout):
 
 class FoldReq:
     """The GroupNorm fold that follows a layer, requested together with the layer: channels = columns
-    [col0, col0 + C0) of that layer's output (+ the first columns of `second` = (partial, col0, C, tpb, mult)).
+    [col0, col0 + C0) of that layer's output (+ the columns of `second`, a Window of another launch's statistics).
     (Round 3 carried such folds inside the producing launch -- per-batch-element device tickets, the completing
     workgroup folds -- and measured it slower at every size; the request object stayed because it keeps
     the producer and its GroupNorm in one place.)"""
@@ -747,25 +766,120 @@ class FoldReq:
 
     @property
     def C(self):
-        return self.C0 + (self.second[2] if self.second else 0)
+        return self.C0 + (self.second.C if self.second else 0)
 
-    def launch(self, partial, tpb, B, sub=None):
-        """pdr_gn_fold over this request's statistics -> (scale, shift).  sub: `partial` was produced by a tile subset
-        (LayerOut.sub); `second` may carry its own as a sixth element."""
-        parts = [(partial, self.col0, self.C0, tpb, self.mult0, sub)] + ([self.second] if self.second else [])
+    def launch(self, stats, B):
+        """pdr_gn_fold over this request's window of `stats` (the producing layer's Stats) -> (scale, shift)."""
+        parts = [stats.window(self.col0, self.C0, self.mult0)] + ([self.second] if self.second else [])
         return self.norm.fold(parts, B, self.C, self.n)
 
 
+def _stats_rows(lib, act, conv, stats):
+    """Where the statistics of a layer over `act` go -> (rows of `partial` per cloud, twin_stats).  Plain: one row per
+    tile.  Deduplicated (act.dd): the tile subset's rows, then the per-query rows' -- twin_stats: written by the
+    per-query launch itself (pdr_layer_in_t.wrow0 / wmul), one per tile of that launch, whatever tile height it
+    picks; else pdr_weighted_moments' groups of 128 rows.  (The paired launch has a layout of its own: _launch_pair.)"""
+    tm = lib.pdr_fused_layer_tile_rows(act.rpb, conv.Cout)
+    tpb = (act.rpb + tm - 1) // tm
+    dd = act.dd
+    if dd is None:
+        return tpb, False
+    assert tm == 128 and tpb == dd.tpb, (tm, tpb, dd.tpb)
+    twin_stats = act.twin is not None and stats and TWIN_STATS and act.twin.wrow0 is not None
+    tmd = lib.pdr_fused_layer_tile_rows(dd.m, conv.Cout)
+    return dd.tpb + ((dd.m + tmd - 1) // tmd if twin_stats else dd.tpbd), twin_stats
+
+
+def _launch_pair(lib, act, conv, Y, y_ptr, ldy, stats, rc0):
+    """Both row sets of a deduplicated layer in ONE launch (128-row tiles for the per-query rows too: their statistics
+    rows follow the tile subset's) -> LayerOut, or None when the layer runs as two launches."""
+    dd, tw = act.dd, act.twin
+    if not PAIRED_LAUNCHES or _PRECISION[0] != "f32" or act.radd is not None or \
+            not conv.pair_ok.get((act.rpb, dd.m), True):
+        return None
+    tpb_p = dd.tpb + (dd.m + 127) // 128
+    part_p = torch.empty((act.B * tpb_p, conv.Cout, 2), dtype=torch.float32, device=Y.device) if stats else None
+    Yd = torch.empty((tw.P, ldy), dtype=torch.float32, device=Y.device)
+    li, li2 = act.struct(tpb_p if stats else 0), tw.struct(tpb_p if stats else 0)
+    # only where the per-query launch runs on the wave-specialised 128-row tiles anyway (the 1024- / 2048-query
+    # levels): the deep levels' per-query rows have launches of their own size (DESIGN.md 4.9) that beat riding on
+    # 128-row tiles by more than the launch they would save (measured: all levels paired 5.78 vs 5.75 ms unpaired)
+    plan = (ctypes.c_int * 8)()
+    rc = lib.pdr_fused_layer_plan(ctypes.byref(li2), tw.P, conv.Cin, conv.Wt.data_ptr(), conv.ldw, conv.Cout,
+                                  Yd.data_ptr(), ldy, plan)
+    if rc == _lib.PDR_OK and plan[0] == 1 and plan[7] == 0 and plan[1] in (2, 4, 7, 8):
+        rc = lib.pdr_fused_layer_pair(ctypes.byref(li), act.P, ctypes.byref(li2), tw.P, conv.Cin, conv.Wt.data_ptr(),
+                                      conv.ldw, conv.bias.data_ptr(), conv.Cout, y_ptr, ldy, Yd.data_ptr(), ldy,
+                                      part_p.data_ptr() if stats else None,
+                                      _ptr(part_p, dd.tpb * conv.Cout * 2) if stats else None, rc0, _stream())
+        if rc == _lib.PDR_OK:
+            return LayerOut(Y, Stats(part_p, tpb_p, (dd.nvalid[0], dd.tpb) if stats else None), twin=Yd, dd=dd)
+        if rc != _lib.PDR_EUNSUPPORTED:
+            _lib.check(rc, "fused_layer_pair")
+    conv.pair_ok[(act.rpb, dd.m)] = False                   # (not asked again for this shape)
+    return None
+
+
+def _launch_exact(lib, act, conv, li, y_ptr, ldy, partial_ptr, rc0):
+    """pdr_fused_layer; returns the pdr_layer_in_t that was launched: `li`, or that of the plain sources a kNN-form
+    gathered source was materialised into."""
+    def launch():
+        return lib.pdr_fused_layer(ctypes.byref(li), act.P, conv.Cin, conv.Wt.data_ptr(), conv.ldw,
+                                   conv.bias.data_ptr(), conv.Cout, y_ptr, ldy, partial_ptr, rc0, _stream())
+    rc = launch()
+    if rc == _lib.PDR_EUNSUPPORTED and act.gs1 is not None and act.first is not None:
+        # a kNN-form gathered source reached a tile shape without a wave-specialised kernel: materialise the
+        # columns it reads (one pdr_gather_add window per segment) and run the layer on plain sources
+        def dense(sg):
+            return Seg(act.first.materialise(sg.off, sg.C), 0, sg.C, _pad4(sg.C)) if sg.gathered else sg
+        plain_act = Act([dense(sg) for sg in act.segs], act.P, act.B, act.rpb, scale=act.scale, shift=act.shift,
+                        add=act.add, add_ld=act.add_ld, radd=None if act.radd is None else dense(act.radd),
+                        pre_relu=act.pre_relu, post_relu=act.post_relu)
+        plain_act.ss_ld, plain_act.oadd = act.ss_ld, act.oadd
+        li = plain_act.struct()
+        rc = launch()
+    _lib.check(rc, "fused_layer")
+    return li
+
+
+def _launch(lib, act, conv, Y, y_ptr, ldy, partial_ptr, rc0, partial_tpb=0, weighted=True):
+    """One layer launch over `act` into Y: on split-f16 arithmetic where the forward in flight asks for it and a tile
+    variant carries the layer, else the exact kernel; its walk direction is recorded for its consumers."""
+    li = act.struct(partial_tpb, weighted)
+    if not _launch_split(lib, act, conv, li, y_ptr, ldy, partial_ptr, rc0):
+        li = _launch_exact(lib, act, conv, li, y_ptr, ldy, partial_ptr, rc0)
+    _WALK[Y.data_ptr()] = li.walk_reverse
+
+
+def _launch_twin(lib, act, conv, ldy, rc0, stats, twin_stats, partial, tpb):
+    """The same layer over the per-query rows of a deduplicated block (first neighbour of every query): its rows stand
+    for the K copies in the skipped tiles -- moments weighted by K there, 0 elsewhere.  -> (Yd, Stats.sub)."""
+    dd, tw = act.dd, act.twin
+    Yd = torch.empty((tw.P, ldy), dtype=torch.float32, device=conv.Wt.device)
+    if twin_stats:
+        # ... computed by that launch itself (pdr_layer_in_t.wrow0 / wmul) into the rows behind the tile subset's;
+        # the fold skips the rows of the tiles the subset skipped (Stats.sub)
+        _launch(lib, tw, conv, Yd, Yd.data_ptr(), ldy, _ptr(partial, dd.tpb * conv.Cout * 2), rc0, partial_tpb=tpb)
+        return Yd, (dd.nvalid[0], dd.tpb)
+    _launch(lib, tw, conv, Yd, Yd.data_ptr(), ldy, None, rc0, weighted=False)
+    if stats:
+        dd.moments(Yd, conv.Cout, rc0, partial)
+    return Yd, None
+
+
 def run_layer(act, conv, stats=False, relu_col0=None, extra_rows=0, out=None, fold=None, stats_into=None):
-    """Y (P, Cout) = prologue(act) . Wt + bias; returns (Y, partial or None, tiles_per_batch).
+    """Y (P, Cout) = prologue(act) . Wt + bias -> LayerOut (Y, stats = Stats(partial or None, rows per cloud, subset)).
     extra_rows: zero rows appended to Y (the zero row of a gathered table); out = (tensor, col0): write into
     columns [col0, col0 + ldy') of an existing (P, ld) tensor instead of allocating.
-    fold: a FoldReq -- returns (Y, partial, tiles_per_batch, (scale, shift)): the GroupNorm fold (pdr_gn_fold) of this
-    layer's statistics is launched right behind it.
+    fold: a FoldReq -- the GroupNorm fold (pdr_gn_fold) of this layer's statistics is launched right behind it,
+    LayerOut.folded = (scale, shift).
     stats_into = (partial, first row, rows per cloud): the statistics go to rows [b rows_per_cloud + first row + tile] of
-    an existing partial tensor (the per-query launch of a deduplicated layer, behind the tile subset's rows)."""
+    an existing partial tensor.
+    A deduplicated activation (act.dd, act.twin) runs over its tile subset and over its per-query rows, as one paired
+    launch or two (LayerOut.twin, LayerOut.dd); where the statistics rows of both go: _stats_rows."""
     lib = _lib.load()
     assert act.C == conv.Cin, (act.C, conv.Cin)
+    assert act.dd is None or (out is None and not extra_rows)
     ldy = _ldy(conv.Cout)
     if out is not None:
         Y, ycol0 = out
@@ -775,98 +889,28 @@ def run_layer(act, conv, stats=False, relu_col0=None, extra_rows=0, out=None, fo
         if extra_rows:
             Y[act.P:].zero_()
         y_ptr = Y.data_ptr()
-    tm = lib.pdr_fused_layer_tile_rows(act.rpb, conv.Cout)
-    tpb = (act.rpb + tm - 1) // tm
-    dd = act.dd
     stats = stats or fold is not None
-    twin_stats = dd is not None and act.twin is not None and stats and TWIN_STATS and act.twin.wrow0 is not None
-    if dd is not None:
-        assert tm == 128 and tpb == dd.tpb and out is None and not extra_rows, (tm, tpb, dd.tpb)
-        # rows of `partial` per cloud: the tile subset's + the per-query rows' (TWIN_STATS: one per tile of the
-        # per-query launch, whatever tile height that launch picks; else pdr_weighted_moments' groups of 128 rows)
-        tmd = lib.pdr_fused_layer_tile_rows(dd.m, conv.Cout)
-        tpb = dd.tpb + ((dd.m + tmd - 1) // tmd if twin_stats else dd.tpbd)
-    twin_ok = dd is not None and act.twin is not None
-    if PAIRED_LAUNCHES and twin_ok and (twin_stats or not stats) and stats_into is None and \
-            _PRECISION[0] == "f32" and act.radd is None and conv.__dict__.get("_pair_ok", {}).get((act.rpb, dd.m), True):
-        # ---- both row sets in one launch (128-row tiles for the per-query rows too: their statistics rows follow)
-        tw = act.twin
-        tpb_p = dd.tpb + (dd.m + 127) // 128
-        part_p = torch.empty((act.B * tpb_p, conv.Cout, 2), dtype=torch.float32, device=Y.device) if stats else None
-        act.ptpb = tw.ptpb = tpb_p if stats else 0
-        Yd = torch.empty((tw.P, ldy), dtype=torch.float32, device=Y.device)
-        li, li2 = act.struct(), tw.struct()
-        rc0 = conv.Cout if relu_col0 is None else relu_col0
-        # only where the per-query launch runs on the wave-specialised 128-row tiles anyway (the 1024- / 2048-query
-        # levels): the deep levels' per-query rows have launches of their own size that beat riding on
-        # 128-row tiles by more than the launch they would save (measured: all levels paired 5.78 vs 5.75 ms unpaired)
-        plan = (ctypes.c_int * 8)()
-        ok = lib.pdr_fused_layer_plan(ctypes.byref(li2), tw.P, conv.Cin, conv.Wt.data_ptr(), conv.ldw, conv.Cout,
-                                      Yd.data_ptr(), ldy, plan) == _lib.PDR_OK and plan[0] == 1 and plan[7] == 0 and \
-            plan[1] in (2, 4, 7, 8)
-        rc = _lib.PDR_EUNSUPPORTED if not ok else lib.pdr_fused_layer_pair(ctypes.byref(li), act.P, ctypes.byref(li2), tw.P, conv.Cin, conv.Wt.data_ptr(),
-                                      conv.ldw, conv.bias.data_ptr(), conv.Cout, y_ptr, ldy, Yd.data_ptr(), ldy,
-                                      part_p.data_ptr() if stats else None,
-                                      _ptr(part_p, dd.tpb * conv.Cout * 2) if stats else None, rc0, _stream())
-        tw.ptpb = 0
-        if rc == _lib.PDR_OK:
-            sub = (dd.nvalid[0], dd.tpb) if stats else None
-            if fold is None:
-                return LayerOut((Y, part_p, tpb_p), twin=Yd, dd=dd, sub=sub)
-            return LayerOut((Y, part_p, tpb_p, fold.launch(part_p, tpb_p, act.B, sub=sub)), twin=Yd, dd=dd, sub=sub)
-        if rc != _lib.PDR_EUNSUPPORTED:
-            _lib.check(rc, "fused_layer_pair")
-        conv.__dict__.setdefault("_pair_ok", {})[(act.rpb, dd.m)] = False      # (not asked again for this shape)
-    partial = partial_ptr = None
-    act.ptpb = 0
-    if stats_into is not None:
-        partial, row0, act.ptpb = stats_into
-        partial_ptr = _ptr(partial, row0 * conv.Cout * 2)
-    elif stats:
-        partial = torch.empty((act.B * tpb, conv.Cout, 2), dtype=torch.float32, device=Y.device)
-        partial_ptr = partial.data_ptr()
-        act.ptpb = tpb if dd is not None else 0
-    li = act.struct()
     rc0 = conv.Cout if relu_col0 is None else relu_col0
-    done = _run_layer_split(lib, act, conv, li, y_ptr, ldy, partial_ptr, rc0)
-    if not done:
-        rc = lib.pdr_fused_layer(ctypes.byref(li), act.P, conv.Cin, conv.Wt.data_ptr(), conv.ldw,
-                                 conv.bias.data_ptr(), conv.Cout, y_ptr, ldy, partial_ptr, rc0, _stream())
-        if rc == _lib.PDR_EUNSUPPORTED and act.gs1 is not None and act.first is not None:
-            # a kNN-form gathered source reached a tile shape without a wave-specialised kernel: materialise the
-            # columns it reads (one pdr_gather_add window per segment) and run the layer on plain sources
-            def dense(sg):
-                return (act.first.materialise(sg[1], sg[2]), 0, sg[2], _pad4(sg[2]), 1) if len(sg) > 5 and sg[5] else sg
-            segs = [dense(sg) for sg in act.segs]
-            plain_act = Act(segs, act.P, act.B, act.rpb, scale=act.scale, shift=act.shift, add=act.add,
-                            add_ld=act.add_ld, radd=None if act.radd is None else dense(act.radd),
-                            pre_relu=act.pre_relu, post_relu=act.post_relu)
-            plain_act.ss_ld, plain_act.oadd = act.ss_ld, act.oadd
-            li = plain_act.struct()
-            rc = lib.pdr_fused_layer(ctypes.byref(li), act.P, conv.Cin, conv.Wt.data_ptr(), conv.ldw,
-                                     conv.bias.data_ptr(), conv.Cout, y_ptr, ldy, partial_ptr, rc0, _stream())
-        _lib.check(rc, "fused_layer")
-    _WALK[Y.data_ptr()] = li.walk_reverse
-    Yd = sub = None
-    if dd is not None and act.twin is not None:
-        # the same layer over the per-query rows (first neighbour of every query): its rows stand for the K copies
-        # in the skipped tiles -- moments weighted by K there, 0 elsewhere
-        if twin_stats:
-            # ... computed by that launch itself (pdr_layer_in_t.wrow0 / wmul) into the rows behind the tile subset's;
-            # the fold skips the rows of the tiles the subset skipped (LayerOut.sub)
-            Yd = run_layer(act.twin, conv, relu_col0=relu_col0, stats_into=(partial, dd.tpb, tpb))[0]
-            sub = (dd.nvalid[0], dd.tpb)
-        else:
-            saved, act.twin.wrow0 = act.twin.wrow0, None
-            Yd = run_layer(act.twin, conv, relu_col0=relu_col0)[0]
-            act.twin.wrow0 = saved
-            if stats:
-                dd.moments(Yd, conv.Cout, rc0, partial)
-    else:
-        dd = None
-    if fold is None:
-        return LayerOut((Y, partial, tpb), twin=Yd, dd=dd, sub=sub)
-    return LayerOut((Y, partial, tpb, fold.launch(partial, tpb, act.B, sub=sub)), twin=Yd, dd=dd, sub=sub)
+    tpb, twin_stats = _stats_rows(lib, act, conv, stats)
+    dd = act.dd if act.twin is not None else None
+    lo = None
+    if dd is not None and (twin_stats or not stats) and stats_into is None:
+        lo = _launch_pair(lib, act, conv, Y, y_ptr, ldy, stats, rc0)
+    if lo is None:
+        partial, row0, ptpb = None, 0, 0
+        if stats_into is not None:
+            partial, row0, ptpb = stats_into
+        elif stats:
+            partial = torch.empty((act.B * tpb, conv.Cout, 2), dtype=torch.float32, device=Y.device)
+            ptpb = tpb if act.dd is not None else 0
+        _launch(lib, act, conv, Y, y_ptr, ldy, None if partial is None else _ptr(partial, row0 * conv.Cout * 2), rc0,
+                partial_tpb=ptpb)
+        Yd, sub = _launch_twin(lib, act, conv, ldy, rc0, stats, twin_stats, partial, tpb) if dd is not None else \
+            (None, None)
+        lo = LayerOut(Y, Stats(partial, tpb, sub), twin=Yd, dd=dd)
+    if fold is not None:
+        lo.folded = fold.launch(lo.stats, act.B)
+    return lo
 
 
 def materialize(act):
@@ -874,7 +918,7 @@ def materialize(act):
     # tile subset, may read it)
     assert act.dd is None, "materialize() of a deduplicated block's activation"
     lib = _lib.load()
-    out = torch.empty((act.P, act.C), dtype=torch.float32, device=act.segs[0][0].device)
+    out = torch.empty((act.P, act.C), dtype=torch.float32, device=act.segs[0].t.device)
     li = act.struct()
     _lib.check(lib.pdr_apply_act(ctypes.byref(li), act.P, act.C, out.data_ptr(), act.C, _stream()), "apply_act")
     return out
@@ -887,36 +931,33 @@ class Norm:
         gn = mod.group_norm if isinstance(mod, MyGroupNorm) else mod
         self.G, self.Cn, self.eps = gn.num_groups, gn.num_channels, gn.eps
         self.gamma, self.beta = gn.weight.detach().contiguous(), gn.bias.detach().contiguous()
+        self._lab_fold = {}            # LAB_SKIP_FOLD: (B, C, n) -> the first result of that fold
 
     def fold(self, parts, B, C, n):
-        """parts: [(partial, col0, ncols, tiles_per_batch, mult[, sub])] (one or two) covering C channels in order; sub =
-        the subset information of a partial produced by a tile subset.  Returns (scale, shift) of shape (B, C):
-        GroupNorm folded to y = x * scale + shift."""
+        """parts: one or two Window (Stats.window; or their fields as plain tuples) covering C channels in order.
+        Returns (scale, shift) of shape (B, C): GroupNorm folded to y = x * scale + shift."""
         lib = _lib.load()
         dev = self.gamma.device
-        assert 1 <= len(parts) <= 2 and sum(p[2] for p in parts) == C
-        if LAB_SKIP_FOLD:
+        parts = [Window(*p) for p in parts]
+        assert 1 <= len(parts) <= 2 and sum(p.C for p in parts) == C
+        if LAB_SKIP_FOLD and (B, C, n) in self._lab_fold:
             # lab probe (never set in the product): the fold of a call site runs ONCE, later calls reuse its result --
             # wrong values, right shapes: an upper bound on what taking the fold launches out of the step could buy
-            hit = self.__dict__.setdefault("_lab_fold", {}).get((B, C, n))
-            if hit is not None:
-                return hit
+            return self._lab_fold[(B, C, n)]
         scale = torch.empty((B, C), dtype=torch.float32, device=dev)
         shift = torch.empty((B, C), dtype=torch.float32, device=dev)
-        (pa, ca, na, ta, ma), sa = parts[0][:5], (parts[0][5] if len(parts[0]) > 5 else None)
-        sb = None
-        if len(parts) == 2:
-            (pb, cb, nb, tb, mb), sb = parts[1][:5], (parts[1][5] if len(parts[1]) > 5 else None)
-            second = (_ptr(pb, 2 * cb), pb.shape[1], tb, nb, float(mb))
-        else:
-            second = (None, 0, 0, 0, 1.0)
 
-        def sub(v):
-            # statistics of a tile SUBSET (LayerOut.sub / FirstOut.sub): (valid tiles per cloud, main tiles)
-            return (v[0].data_ptr(), v[1]) if v is not None else (None, 0)
-        _lib.check(lib.pdr_gn_fold(_ptr(pa, 2 * ca), pa.shape[1], ta, na, float(ma), *second, B, self.Cn, self.G,
-                                   float(n), float(self.eps), self.gamma.data_ptr(), self.beta.data_ptr(),
-                                   scale.data_ptr(), shift.data_ptr(), *sub(sa), *sub(sb), _stream()), "gn_fold")
+        def window(w):
+            return (_ptr(w.partial, 2 * w.col0), w.partial.shape[1], w.tpb, w.C, float(w.mult)) if w is not None else \
+                (None, 0, 0, 0, 1.0)
+
+        def sub(w):
+            # statistics of a tile SUBSET (Stats.sub): (valid tiles per cloud, main tiles)
+            return (w.sub[0].data_ptr(), w.sub[1]) if w is not None and w.sub is not None else (None, 0)
+        a, b = parts[0], (parts[1] if len(parts) == 2 else None)
+        _lib.check(lib.pdr_gn_fold(*window(a), *window(b), B, self.Cn, self.G, float(n), float(self.eps),
+                                   self.gamma.data_ptr(), self.beta.data_ptr(), scale.data_ptr(), shift.data_ptr(),
+                                   *sub(a), *sub(b), _stream()), "gn_fold")
         if LAB_SKIP_FOLD:
             self._lab_fold[(B, C, n)] = (scale, shift)
         return scale, shift
@@ -1032,13 +1073,14 @@ class FusedMlp:
             last = len(stages) - 1
             assert last not in self.inject
             self.inject[last] = bank.register("c2", mlp.fc_second_condition)
+        self._chain_sync = {}     # chain(): (B, device) -> the cluster counters of pdr_point_chain
 
     def __call__(self, x, bank, relu_stats_extra=True):
-        """x: Act over the grouped input.  Returns (h Act [final activation incl. residual], Y1, part1, tpb1)
-        where Y1 holds [first conv | res conv | extra convs] columns."""
+        """x: Act over the grouped input.  Returns (h Act [final activation incl. residual], first) where the FirstOut
+        `first` holds the [first conv | res conv | extra convs] columns and their statistics."""
         relu0 = self.extra_col0 if relu_stats_extra else None
-        Y1, part1, tpb1, folded = run_layer(x, self.first, relu_col0=relu0, fold=self.first_fold(x.rpb))
-        return self.after_first(Y1, part1, tpb1, x.P, x.B, x.rpb, bank, x, folded=folded)
+        lo = run_layer(x, self.first, relu_col0=relu0, fold=self.first_fold(x.rpb))
+        return self.after_first(FirstOut(Y=lo.Y, stats=lo.stats), x.P, x.B, x.rpb, bank, x, folded=lo.folded)
 
     def chain(self, x, bank):
         """The whole MLP on per-point rows as ONE pdr_point_chain launch -> (P, Clast) tensor, or None when the shapes
@@ -1048,14 +1090,14 @@ class FusedMlp:
                 (self.has_res and self.res_col0 is None) or self.extra_col0 != self.first.Cout or \
                 _PRECISION[0] != "f32" or len(self.norms) > 4:
             return None
-        if any(len(sg) > 5 and sg[5] is not None or sg[4] != 1 for sg in x.segs):
+        if any(sg.gathered or sg.div != 1 for sg in x.segs):
             return None
         lib = _lib.load()
         B, n = x.B, x.rpb
         ch = _lib.PointChain()
         ch.n_layers, ch.n_seg = len(self.norms), len(x.segs)
-        for i, (t, off, C, ld, _) in enumerate(sg[:5] for sg in x.segs):
-            ch.seg[i].ptr, ch.seg[i].C, ch.seg[i].ld = _ptr(t, off), C, ld
+        for i, sg in enumerate(x.segs):
+            ch.seg[i].ptr, ch.seg[i].C, ch.seg[i].ld = _ptr(sg.t, sg.off), sg.C, sg.ld
         convs = [self.first] + self.rest
         keep = []
         for i, (conv, norm) in enumerate(zip(convs, self.norms)):
@@ -1078,7 +1120,7 @@ class FusedMlp:
         out = torch.empty((B * n, self.Clast), dtype=torch.float32, device=dev)
         scratch = torch.empty((max(int(plan[1]), 4),), dtype=torch.float32, device=dev)
         # the cluster counters: zeroed once, left zero by every launch (one buffer per batch size of this block)
-        sync = self.__dict__.setdefault("_chain_sync", {}).get((B, dev))
+        sync = self._chain_sync.get((B, dev))
         if sync is None:
             sync = self._chain_sync[(B, dev)] = torch.zeros((int(plan[2]),), dtype=torch.int32, device=dev)
         ch.out, ch.ldo, ch.scratch, ch.sync = out.data_ptr(), out.shape[1], scratch.data_ptr(), sync.data_ptr()
@@ -1092,25 +1134,24 @@ class FusedMlp:
         """Fold request of the GroupNorm behind the first conv (for whoever launches that conv)."""
         return FoldReq(self.norms[0], self.C1, rpb)
 
-    def after_first(self, Y1, part1, tpb1, P, B, rpb, bank, x=None, folded=None):
-        """Everything behind the first conv, given its output `Y1` (a tensor or a FirstOut) and, when the first
-        conv's launch carried it, the fold of the first GroupNorm (`folded` = (scale, shift))."""
-        first = Y1 if isinstance(Y1, FirstOut) else FirstOut(Y=Y1)
-        part, tpb, part_sub = part1, tpb1, first.sub
+    def after_first(self, first, P, B, rpb, bank, x=None, folded=None):
+        """Everything behind the first conv, given its output and statistics (`first`, a FirstOut) and, when the first
+        conv's launch carried it, the fold of the first GroupNorm (`folded` = (scale, shift), or a thunk launching it).
+        Returns (h, first)."""
+        stats = first.stats
         cur = first.attach(Act([first.seg(0, self.C1)], P, B, rpb))
         if callable(folded):
             folded = folded()
         for i, norm in enumerate(self.norms):
             C = cur.C
-            scale, shift = folded if folded is not None else norm.fold([(part, 0, C, tpb, 1.0, part_sub)], B, C, rpb)
+            scale, shift = folded if folded is not None else norm.fold([stats.window(0, C)], B, C, rpb)
             cur.scale, cur.shift, cur.post_relu = scale, shift, True
             inj = bank.get(self.inject.get(i))
             if inj is not None:
                 cur.add, cur.add_ld = inj[0][:, inj[1]:], inj[2]
             if i < len(self.rest):
                 lo = run_layer(cur, self.rest[i], fold=FoldReq(self.norms[i + 1], self.rest[i].Cout, rpb))
-                _, part, tpb, folded = lo
-                part_sub = lo.sub
+                stats, folded = lo.stats, lo.folded
                 cur = act_from(lo, self.rest[i].Cout, P, B, rpb)
         if self.has_res:
             if self.res_col0 is not None:
@@ -1121,7 +1162,7 @@ class FusedMlp:
                         x.add is not None:
                     raise NotImplementedError("identity residual over a composite input")
                 cur.radd = x.segs[0]
-        return cur, first, part1, tpb1
+        return cur, first
 
 
 class FusedAttention:
@@ -1150,41 +1191,41 @@ class FusedAttention:
         self.D = self.w2.Cout
 
     def values(self, h, B, npoint, K):
-        """Value half (independent of the query features): value conv + its GroupNorm fold -> (V, scale, shift, twin)."""
-        if self.v_norm is None:
-            lo = run_layer(h, self.v)
-            return lo[0], None, None, lo.twin
-        lo = run_layer(h, self.v, fold=FoldReq(self.v_norm, self.D, npoint * K))
-        V, _, _, (vs, vt) = lo
-        return V, vs, vt, lo.twin                    # (twin: the per-query value rows of a deduplicated block)
+        """Value half (independent of the query features): value conv + its GroupNorm fold -> (V, scale, shift, twin);
+        twin: the per-query value rows of a deduplicated block.  (Not the LayerOut: its statistics are done with.)"""
+        lo = run_layer(h, self.v, fold=FoldReq(self.v_norm, self.D, npoint * K) if self.v_norm is not None else None)
+        return (lo.Y, *(lo.folded or (None, None)), lo.twin)
 
     def query_conv(self, query, B, npoint):
         """The query conv and its statistics (the first launch of __call__), for callers that issue it ahead."""
         return run_layer(plain(query, B, npoint), self.q, stats=True, relu_col0=0)
 
-    def __call__(self, query, h, Y1, part1, tpb1, key_col0, counts, B, npoint, K, values=None, sorted_q=None,
+    def __call__(self, query, h, first, key_col0, counts, B, npoint, K, values=None, sorted_q=None,
                  query_rows=None, q_ahead=None):
-        """query: (B*npoint, Cq) tensor; h: Act (value input); key = Y1[:, key_col0:key_col0+C2];
+        """query: (B*npoint, Cq) tensor; h: Act (value input); key = columns [key_col0, key_col0 + C2) of the block's
+        first conv `first` (a FirstOut: output + statistics);
         values: result of self.values(h, ...) when it was evaluated ahead of time.
+        q_ahead: the LayerOut of query_conv (or a thunk yielding it) when the query conv was launched ahead.
         query_rows: int32 (B*npoint) -- `query` is in another row order than the block's positions (QUERIES_IN_PLACE:
         the original order of a block evaluated on sorted queries): position p's query is row query_rows[p / K]."""
         lib = _lib.load()
         P = B * npoint * K
-        first = Y1 if isinstance(Y1, FirstOut) else FirstOut(Y=Y1)
         # GroupNorm over [q.expand(K) | key]: the q half's moments count K times, the key half's come from the first
         # conv's launch -- both folded at the end of the q conv's launch
         Ct = self.C1 + self.C2
         n1_fold = FoldReq(self.n1, self.C1, npoint * K, mult0=float(K),
-                          second=(part1, key_col0, self.C2, tpb1, 1.0, first.sub))
+                          second=first.stats.window(key_col0, self.C2))
         if q_ahead is not None:                      # the query conv was launched ahead (query_conv): join, then fold
-            q, qpart, qtpb = q_ahead() if callable(q_ahead) else q_ahead
-            s, t = n1_fold.launch(qpart, qtpb, B)
+            ql = q_ahead() if callable(q_ahead) else q_ahead
+            s, t = n1_fold.launch(ql.stats, B)
         else:
-            q, qpart, qtpb, (s, t) = run_layer(plain(query, B, npoint), self.q, relu_col0=0, fold=n1_fold)
+            ql = run_layer(plain(query, B, npoint), self.q, relu_col0=0, fold=n1_fold)
+            s, t = ql.folded
+        q = ql.Y
         if SPLIT_QUERY_CONV and (K & (K - 1)) == 0:
-            zq = Act([(q, 0, self.C1, q.shape[1], 1)], B * npoint, B, npoint, scale=s, shift=t, pre_relu=True)
+            zq = Act([Seg(q, 0, self.C1, q.shape[1])], B * npoint, B, npoint, scale=s, shift=t, pre_relu=True)
             zq.ss_ld = Ct
-            Z, _, _ = run_layer(zq, self.w1_q)
+            Z = run_layer(zq, self.w1_q).Y
             a = first.attach(Act([first.seg(key_col0, self.C2)], P, B, npoint * K, scale=s[:, self.C1:],
                                  shift=t[:, self.C1:], pre_relu=True))
             a.ss_ld = Ct
@@ -1197,12 +1238,12 @@ class FusedAttention:
                     a.twin.oadd_rows = query_rows
             lo1 = run_layer(a, self.w1_k, relu_col0=0, fold=FoldReq(self.n2, self.w1.Cout, npoint * K))
         else:
-            a = first.attach(Act([(q, 0, self.C1, q.shape[1], K), first.seg(key_col0, self.C2)], P, B,
+            a = first.attach(Act([Seg(q, 0, self.C1, q.shape[1], K), first.seg(key_col0, self.C2)], P, B,
                                  npoint * K, scale=s, shift=t, pre_relu=True))
             lo1 = run_layer(a, self.w1, relu_col0=0, fold=FoldReq(self.n2, self.w1.Cout, npoint * K))
-        S1, _, _, (s, t) = lo1
+        S1, (s, t) = lo1.Y, lo1.folded
         mark("  blk:main_scores_ready", True)
-        score_in = Act([(S1, 0, self.w1.Cout, S1.shape[1], 1)], P, B, npoint * K, scale=s, shift=t, pre_relu=True)
+        score_in = Act([Seg(S1, 0, self.w1.Cout, S1.shape[1])], P, B, npoint * K, scale=s, shift=t, pre_relu=True)
         dd = lo1.dd
         score_in.dd = dd                             # the pooled launch walks the block's tile subset
         # a block evaluated on sorted queries (SortedQueries): the pooled launch and the patch write every query's row
@@ -1240,16 +1281,11 @@ class FusedAttention:
             li = score_in.struct()
             if out_rows is not None:
                 li.out_rows = out_rows.data_ptr()     # sorted queries: pooled rows go back to their original places
-            if _PRECISION[0] == "split_f16" and self.w2.Cin >= SPLIT_MIN_CIN and \
-                    lib.pdr_fused_layer_variant(npoint * K, self.D) in SPLIT_VARIANTS:
+            variant = lib.pdr_fused_layer_variant(npoint * K, self.D) \
+                if _PRECISION[0] == "split_f16" and self.w2.Cin >= SPLIT_MIN_CIN else None
+            if variant in SPLIT_VARIANTS:
                 # score conv on split-f16 arithmetic too (128-column tiles; else the exact kernel below)
-                variant = lib.pdr_fused_layer_variant(npoint * K, self.D)
-                TN = 64 if variant == 8 else 128
-                cache = self.w2.__dict__.setdefault("_f16x3", {})
-                key = (self.w2.Cin, TN)
-                if key not in cache:
-                    cache[key] = pack_f16x3(self.w2.Wt, self.w2.Cout, key[:1], TN)
-                img, nch = cache[key]
+                img, nch = self.w2.f16x3_image([self.w2.Cin], 64 if variant == 8 else 128)
                 rc = lib.pdr_fused_layer_pool_f16x3(ctypes.byref(li), P, self.w2.Cin, img.data_ptr(), nch,
                                                      self.w2.bias.data_ptr(), self.D, V.data_ptr(), V.shape[1], vsp, vtp,
                                                      int(self.v_relu), cptr, K, out.data_ptr(), self.D, _stream())
@@ -1261,7 +1297,7 @@ class FusedAttention:
                                                 int(self.v_relu), cptr, K, out.data_ptr(), self.D, _stream()),
                        "fused_layer_pool")
             return patch()
-        scores, _, _ = run_layer(score_in, self.w2)
+        scores = run_layer(score_in, self.w2).Y
         _lib.check(lib.pdr_attention_pool(scores.data_ptr(), scores.shape[1], V.data_ptr(), V.shape[1], vsp, vtp,
                                           int(self.v_relu), cptr, B, npoint, K, self.D, out.data_ptr(), _stream()),
                    "attention_pool")
@@ -1274,6 +1310,9 @@ class _RawConv:
     def __init__(self, Wt, bias, Cout):
         self.Wt, self.bias = Wt.contiguous(), bias.contiguous()
         self.Cin, self.ldw, self.Cout = Wt.shape[0], Wt.shape[1], Cout
+        self.f16x3, self.pair_ok = {}, {}            # (as Conv's)
+
+    f16x3_image = Conv.f16x3_image
 
 
 class SplitFirstConv:
@@ -1293,6 +1332,7 @@ class SplitFirstConv:
         Wt, bias, Cout, dev = first.Wt, first.bias, first.Cout, first.Wt.device
         self.Cout, self.ld = Cout, first.ldw
         self._tables = {}
+        self._halves = {}                                  # _table_halves: Cm -> (late, early)
         zero3 = torch.zeros((3, first.ldw), device=dev)
         zb = torch.zeros_like(bias)
         pad_bias = torch.zeros(first.ldw, device=dev)
@@ -1330,7 +1370,7 @@ class SplitFirstConv:
         balls).  Depends on the SOURCE cloud only, so callers whose source is static across reverse steps (the
         feature-transfer blocks read the retained condition features) compute it once per batch."""
         B, n, Cs = src_feats_cl.shape
-        u_in = Act(feature_segments(src_feats_cl) + [(xyz4(src_xyz), 0, 3, 4, 1)], B * n, B, n)
+        u_in = Act(feature_segments(src_feats_cl) + [Seg(xyz4(src_xyz), 0, 3, 4)], B * n, B, n)
         # the table lives in a buffer owned by this block (one per shape), zeroed ONCE: the GEMM rewrites rows
         # [0, B n) every call and nothing ever writes the trailing zero row, so no fill launch per step
         key = (B * n + 1, _ldy(self.U.Cout))
@@ -1342,18 +1382,18 @@ class SplitFirstConv:
 
     def _table_halves(self, Cm):
         """(late, early) convs of the per-source table split behind its first Cm input channels."""
-        cache = self.__dict__.setdefault("_halves", {})
-        if Cm not in cache:
+        if Cm not in self._halves:
             zb = torch.zeros_like(self.U.bias)
-            cache[Cm] = (_RawConv(self.U.Wt[:Cm], self.U.bias, self.U.Cout), _RawConv(self.U.Wt[Cm:], zb, self.U.Cout))
-        return cache[Cm]
+            self._halves[Cm] = (_RawConv(self.U.Wt[:Cm], self.U.bias, self.U.Cout),
+                                _RawConv(self.U.Wt[Cm:], zb, self.U.Cout))
+        return self._halves[Cm]
 
     def source_table_early(self, Cm, early_feats_cl, src_xyz):
         """U_early (B n, ld) = [early features | xyz] . W[Cm:]: the part of source_table() that does not read the first
         Cm channels of the source features (SPLIT_SOURCE_TABLES)."""
         B, n, _ = early_feats_cl.shape
-        u_in = Act(feature_segments(early_feats_cl) + [(xyz4(src_xyz), 0, 3, 4, 1)], B * n, B, n)
-        return run_layer(u_in, self._table_halves(Cm)[1])[0]
+        u_in = Act(feature_segments(early_feats_cl) + [Seg(xyz4(src_xyz), 0, 3, 4)], B * n, B, n)
+        return run_layer(u_in, self._table_halves(Cm)[1]).Y
 
     def source_table_late(self, late_feats_cl, part):
         """U = late features . W[:Cm] + U_early, into the block's table buffer (see source_table)."""
@@ -1381,9 +1421,10 @@ class SplitFirstConv:
 
     def __call__(self, src_feats_cl, src_xyz, query_xyz, idx32, counts, K, relu_col0, s1=None, s2=None,
                  virtual=False, res=None, U=None, V2=None, fold=None, dd=None):
-        """-> (Y1, partial, tiles_per_batch, folded).  Y1 = (B*m*K, ld) tensor, or with virtual=True a FirstOut that
-        consumers read as a gathered source (only the GroupNorm moments are computed here).  fold: FoldReq of the
-        GroupNorm behind this conv; folded = a thunk launching that fold -> (scale, shift), None without request."""
+        """-> (first, folded).  first = a FirstOut with this conv's statistics: over the (B*m*K, ld) output, or with
+        virtual=True in the form that consumers read as a gathered source (only the GroupNorm moments are computed
+        here).  fold: FoldReq of the GroupNorm behind this conv; folded = a thunk launching that fold -> (scale, shift),
+        None without request."""
         lib = _lib.load()
         B, n, Cs = src_feats_cl.shape
         m = query_xyz.shape[1]
@@ -1436,11 +1477,11 @@ class SplitFirstConv:
 
         # (a thunk: the fold is launched by whoever consumes it, i.e. on the stream that runs the rest of the MLP)
         sub = [None]                                   # set by gather_add: the statistics of a tile subset
-        folded = (lambda: fold.launch(partial, ptpb, B, sub=sub[0])) if fold is not None else None
+        folded = (lambda: fold.launch(Stats(partial, ptpb, sub[0]), B)) if fold is not None else None
 
         if not virtual:
             gather_add(Y.data_ptr(), ld, 0, -1)
-            return Y, partial, tpb, folded
+            return FirstOut(Y=Y, stats=Stats(partial, tpb)), folded
         # virtual: GroupNorm moments of every column, but only the residual columns (a row-wise add in their
         # consumer, which stays a plain read) are written -- one pass
         Yres = None
@@ -1464,14 +1505,14 @@ class SplitFirstConv:
                 B, rpb, K, self.Cout, Yc.data_ptr(), Yc.shape[1], None, relu_col0, col0, C, _stream()), "gather_add")
             return Yc
 
-        first = FirstOut(U=U, V2=V2, ld=ld, has_v0=has_v0, idx=idx32, counts=counts if has_v0 else None, K=K,
-                         nsrc=n, zrow=B * n, Yres=Yres, res_col0=res[0] if res else 0,
-                         res_cols=res[1] if res else 0, s1=s1, s2=s2, r1=self.r1 if s1 is not None else None,
-                         r2=self.r2 if s1 is not None else None, materialise=materialise)
+        first = FirstOut(stats=Stats(partial, ptpb, sub[0]), U=U, V2=V2, ld=ld, has_v0=has_v0, idx=idx32,
+                         counts=counts if has_v0 else None, K=K, nsrc=n, zrow=B * n, Yres=Yres,
+                         res_col0=res[0] if res else 0, res_cols=res[1] if res else 0, s1=s1, s2=s2,
+                         r1=self.r1 if s1 is not None else None, r2=self.r2 if s1 is not None else None,
+                         materialise=materialise)
         if dd is not None:
             first.dd, first.deg = dd, Yd
-        first.sub = sub[0]
-        return first, partial, ptpb, folded
+        return first, folded
 
 
 def group_build(feats_cl, xyz, new_xyz, idx, counts, patch_empty, with_abs, with_centre):
@@ -1506,9 +1547,9 @@ class Cat:
 
 
 def feature_segments(feats_cl):
-    """Input segments (tensor, offset, C, ld, row_div) of a (B, n, C) feature tensor or a Cat of two."""
+    """Input segments of a (B, n, C) feature tensor or a Cat of two."""
     parts = feats_cl.parts if isinstance(feats_cl, Cat) else (feats_cl,)
-    return [(xyz4(t), 0, t.shape[2], _pad4(t.shape[2]), 1) for t in parts]
+    return [Seg(xyz4(t), 0, t.shape[2], _pad4(t.shape[2])) for t in parts]
 
 
 def gather_rows(src_cl, idx):
@@ -1541,6 +1582,7 @@ class FusedGroupedBlock:
         self.split = None   # built lazily (needs the source feature width)
         self.static_U = None
         self.dedup = False  # evaluate one-point neighbourhoods once (set for the x_t branch, see Dedup)
+        self._t128 = {}     # _tiles_128: rows per cloud -> bool
 
     _WS_ON = []
 
@@ -1559,12 +1601,11 @@ class FusedGroupedBlock:
 
     def _tiles_128(self, rpb):
         """Every per-neighbour layer of this block runs on 128-row tiles (the granularity of a plan)."""
-        key = ("_t128", rpb)
-        if key not in self.__dict__:
+        if rpb not in self._t128:
             tr = _lib.load().pdr_fused_layer_tile_rows
             couts = [c.Cout for c in self.mlp.rest] + [self.att.v.Cout, self.att.w1.Cout, self.att.w2.Cout]
-            self.__dict__[key] = all(tr(rpb, c) == 128 for c in couts)
-        return self.__dict__[key]
+            self._t128[rpb] = all(tr(rpb, c) == 128 for c in couts)
+        return self._t128[rpb]
 
     def _plan(self, idx, counts, B, m, K, sq=None):
         """The Dedup plan of this block's (sorted) neighbourhoods -- `idx` = the sorted index rows of `sq`, the
@@ -1663,19 +1704,18 @@ class FusedGroupedBlock:
         V2 = self._tables_for(V2, sq)          # (tables of another query order: evaluated here instead)
         if USE_SPLIT_FIRST:
             split = self._make_split(src_feats_cl.shape[2])
-            Y1, part1, tpb1, folded = split(src_feats_cl, src_xyz, new_xyz, idx, None if subset else counts, K,
-                                    self.mlp.extra_col0, virtual=USE_VIRTUAL_FIRST,
-                                    res=(self.mlp.res_col0, self.mlp.Clast) if self.mlp.res_col0 is not None else None,
-                                    U=self.static_U, V2=V2, fold=self.mlp.first_fold(m * K),
-                                    dd=self._plan(idx, counts, B, m, K, sq))
-            h, Y1, part1, tpb1 = self.mlp.after_first(Y1, part1, tpb1, B * m * K, B, m * K, bank, folded=folded)
+            first, folded = split(src_feats_cl, src_xyz, new_xyz, idx, None if subset else counts, K,
+                                  self.mlp.extra_col0, virtual=USE_VIRTUAL_FIRST,
+                                  res=(self.mlp.res_col0, self.mlp.Clast) if self.mlp.res_col0 is not None else None,
+                                  U=self.static_U, V2=V2, fold=self.mlp.first_fold(m * K),
+                                  dd=self._plan(idx, counts, B, m, K, sq))
+            h, first = self.mlp.after_first(first, B * m * K, B, m * K, bank, folded=folded)
         else:
             dense_feats = src_feats_cl.dense() if isinstance(src_feats_cl, Cat) else src_feats_cl
             G, Cg = group_build(dense_feats, src_xyz, new_xyz, idx, counts, not subset, self.with_abs,
                                 self.with_centre)
-            h, Y1, part1, tpb1 = self.mlp(plain(G, B, m * K, C=Cg), bank)
-        return dict(h=h, Y1=Y1, part1=part1, tpb1=tpb1, counts=counts, B=B, m=m, K=K, sq=sq,
-                    values=self.att.values(h, B, m, K))
+            h, first = self.mlp(plain(G, B, m * K, C=Cg), bank)
+        return dict(h=h, first=first, counts=counts, B=B, m=m, K=K, sq=sq, values=self.att.values(h, B, m, K))
 
     def finish(self, prep, query_feats_cl):
         B, m, K, sq = prep["B"], prep["m"], prep["K"], prep["sq"]
@@ -1685,9 +1725,8 @@ class FusedGroupedBlock:
                 rows = sq.perm_rows
             else:
                 query_feats_cl = gather_rows(query_feats_cl, sq.perm)
-        out = self.att(query_feats_cl.reshape(B * m, -1), prep["h"], prep["Y1"], prep["part1"], prep["tpb1"],
-                       self.mlp.extra_col0, prep["counts"], B, m, K, values=prep["values"], sorted_q=sq,
-                       query_rows=rows)
+        out = self.att(query_feats_cl.reshape(B * m, -1), prep["h"], prep["first"], self.mlp.extra_col0,
+                       prep["counts"], B, m, K, values=prep["values"], sorted_q=sq, query_rows=rows)
         return out.view(B, m, -1)                 # (rows in the original query order, see FusedAttention)
 
     def __call__(self, src_xyz, src_feats_cl, new_xyz, query_feats_cl, bank, subset, neigh=None, V2=None, U=None,
@@ -1715,24 +1754,24 @@ class FusedGroupedBlock:
             q_ahead = None                     # (made on the original order, but this block gathered its queries)
         if q_ahead is None and QUERY_CONV_AHEAD and SPLIT_QUERY_CONV:
             qf = query_feats_cl.reshape(B * m, -1)
-            q_ahead = _ahead_on_aux(lambda: self.att.query_conv(qf, B, m))
+            q_ahead = _on_aux(lambda: self.att.query_conv(qf, B, m))
         split = self._make_split(src_feats_cl.shape[2])
-        Y1, part1, tpb1, folded = split(src_feats_cl, src_xyz, new_xyz, idx, None if subset else counts, K,
-                                self.mlp.extra_col0, virtual=USE_VIRTUAL_FIRST,
-                                res=(self.mlp.res_col0, self.mlp.Clast) if self.mlp.res_col0 is not None else None,
-                                U=U if U is not None else self.static_U, V2=V2, fold=self.mlp.first_fold(m * K),
-                                dd=self._plan(idx, counts, B, m, K, sq))
+        first, folded = split(src_feats_cl, src_xyz, new_xyz, idx, None if subset else counts, K,
+                              self.mlp.extra_col0, virtual=USE_VIRTUAL_FIRST,
+                              res=(self.mlp.res_col0, self.mlp.Clast) if self.mlp.res_col0 is not None else None,
+                              U=U if U is not None else self.static_U, V2=V2, fold=self.mlp.first_fold(m * K),
+                              dd=self._plan(idx, counts, B, m, K, sq))
 
         mark("  blk:first_conv_stats_done", True)
 
         def chain_a():
             mark("  blk:aux_begin", True)
-            h, _, _, _ = self.mlp.after_first(Y1, part1, tpb1, B * m * K, B, m * K, bank, folded=folded)
+            h, _ = self.mlp.after_first(first, B * m * K, B, m * K, bank, folded=folded)
             r = self.att.values(h, B, m, K)
             mark("  blk:aux_values_done", True)
             return r
-        values = _fork_join(B * m * K, chain_a)
-        out = self.att(query_feats_cl.reshape(B * m, -1), None, Y1, part1, tpb1, self.mlp.extra_col0, counts, B, m, K,
+        values = _on_aux(chain_a)
+        out = self.att(query_feats_cl.reshape(B * m, -1), None, first, self.mlp.extra_col0, counts, B, m, K,
                        values=values, sorted_q=sq, query_rows=rows, q_ahead=q_ahead)
         mark("  blk:pool_done", True)
         return out.view(B, m, -1)                 # (rows in the original query order, see FusedAttention)
@@ -1765,21 +1804,21 @@ class FusedKnnFP:
         q_ahead = None
         if USE_SPLIT_FIRST and QUERY_CONV_AHEAD and SPLIT_QUERY_CONV:
             qf = unknown_feats_cl.reshape(B * n, -1)
-            q_ahead = _ahead_on_aux(lambda: self.att.query_conv(qf, B, n))
+            q_ahead = _on_aux(lambda: self.att.query_conv(qf, B, n))
         if USE_SPLIT_FIRST:
             self._make_split(C)
-            Y1, part1, tpb1, folded = self.split(
+            first, folded = self.split(
                 known_feats_cl, known, unknown, idx, None, K, self.mlp1.extra_col0, s1=d2, s2=wgt, V2=V2, U=U,
                 virtual=USE_VIRTUAL_FIRST and USE_VIRTUAL_KNN,
                 res=(self.mlp1.res_col0, self.mlp1.Clast) if self.mlp1.res_col0 is not None else None,
                 fold=self.mlp1.first_fold(n * K))
             if _PAR["stream"] is not None:
                 def chain_a():
-                    hh, _, _, _ = self.mlp1.after_first(Y1, part1, tpb1, B * n * K, B, n * K, bank, folded=folded)
+                    hh, _ = self.mlp1.after_first(first, B * n * K, B, n * K, bank, folded=folded)
                     return self.att.values(hh, B, n, K)
-                h, values = None, _fork_join(B * n * K, chain_a)
+                h, values = None, _on_aux(chain_a)
             else:
-                h, Y1, part1, tpb1 = self.mlp1.after_first(Y1, part1, tpb1, B * n * K, B, n * K, bank, folded=folded)
+                h, first = self.mlp1.after_first(first, B * n * K, B, n * K, bank, folded=folded)
                 values = None
         else:
             G = torch.empty((B * n * K, _pad4(C + 11)), dtype=torch.float32, device=unknown.device)
@@ -1788,16 +1827,16 @@ class FusedKnnFP:
             _lib.check(lib.pdr_knn_build(known_dense.data_ptr(), C, unknown.data_ptr(), known.data_ptr(),
                                          idx64.data_ptr(), d2.data_ptr(), B, n, n2, K, G.data_ptr(), G.shape[1],
                                          _stream()), "knn_build")
-            h, Y1, part1, tpb1 = self.mlp1(plain(G, B, n * K, C=C + 11), bank)
+            h, first = self.mlp1(plain(G, B, n * K, C=C + 11), bank)
             values = None
-        interp = self.att(unknown_feats_cl.reshape(B * n, -1), h, Y1, part1, tpb1, self.mlp1.extra_col0, None, B, n,
-                          K, values=values, q_ahead=q_ahead)
+        interp = self.att(unknown_feats_cl.reshape(B * n, -1), h, first, self.mlp1.extra_col0, None, B, n, K,
+                          values=values, q_ahead=q_ahead)
         Cs = unknown_feats_cl.shape[2]
-        x2 = Act([(interp, 0, self.att.D, interp.shape[1], 1),
-                  (xyz4(unknown_feats_cl), 0, Cs, _pad4(Cs), 1), (xyz4(unknown), 0, 3, 4, 1)], B * n, B, n)
+        x2 = Act([Seg(interp, 0, self.att.D, interp.shape[1]), Seg(xyz4(unknown_feats_cl), 0, Cs, _pad4(Cs)),
+                  Seg(xyz4(unknown), 0, 3, 4)], B * n, B, n)
         out = self.mlp2.chain(x2, bank)                # one launch for the <= 256-point levels (POINT_CHAINS)
         if out is None:
-            h2, _, _, _ = self.mlp2(x2, bank, relu_stats_extra=False)
+            h2, _ = self.mlp2(x2, bank, relu_stats_extra=False)
             out = materialize(h2)
         return out.view(B, n, -1)
 
@@ -1805,7 +1844,7 @@ class FusedKnnFP:
 def act_colmax(act):
     """(B, C) = max over every batch element's rows of the lazily-activated `act` (pdr_act_colmax)."""
     assert act.dd is None, "act_colmax() of a deduplicated block's activation"
-    out = torch.empty((act.B, act.C), dtype=torch.float32, device=act.segs[0][0].device)
+    out = torch.empty((act.B, act.C), dtype=torch.float32, device=act.segs[0].t.device)
     li = act.struct()
     _lib.check(_lib.load().pdr_act_colmax(ctypes.byref(li), act.P, act.C, out.data_ptr(), _stream()), "act_colmax")
     return out
@@ -1844,13 +1883,12 @@ class FusedPnet2Stage:
     def _mlp(x, stages, B, n):
         """x: Act -> Act of the stage's output (its last GroupNorm + ReLU folded in lazily, if it has one)."""
         (c1, n1), (c2, n2) = stages
-        Y1, _, _, (s, t) = run_layer(x, c1, fold=FoldReq(n1, c1.Cout, n))
-        a1 = Act([(Y1, 0, c1.Cout, Y1.shape[1], 1)], B * n, B, n, scale=s, shift=t, post_relu=True)
+        lo = run_layer(x, c1, fold=FoldReq(n1, c1.Cout, n))
+        a1 = act_from(lo, c1.Cout, B * n, B, n, scale=lo.folded[0], shift=lo.folded[1], post_relu=True)
         if n2 is None:
-            Y2 = run_layer(a1, c2)[0]
-            return Act([(Y2, 0, c2.Cout, Y2.shape[1], 1)], B * n, B, n)
-        Y2, _, _, (s, t) = run_layer(a1, c2, fold=FoldReq(n2, c2.Cout, n))
-        return Act([(Y2, 0, c2.Cout, Y2.shape[1], 1)], B * n, B, n, scale=s, shift=t, post_relu=True)
+            return act_from(run_layer(a1, c2), c2.Cout, B * n, B, n)
+        lo = run_layer(a1, c2, fold=FoldReq(n2, c2.Cout, n))
+        return act_from(lo, c2.Cout, B * n, B, n, scale=lo.folded[0], shift=lo.folded[1], post_relu=True)
 
     def __call__(self, g_in):
         """g_in (B, n, Cin) channel-last -> (B, C_out) global feature."""
@@ -1859,7 +1897,7 @@ class FusedPnet2Stage:
         f = self._mlp(x, self.s1, B, n)
         g = act_colmax(f)                                                   # (B, C1)
         C1 = f.C
-        Y, _, _, ld, _ = f.segs[0]
+        Y, ld = f.segs[0].t, f.segs[0].ld
         dev = g.device
         one = torch.ones((B, C1), device=dev) if f.scale is None else f.scale
         zero = torch.zeros((B, C1), device=dev)
@@ -1872,10 +1910,10 @@ class FusedPnet2Stage:
         while d * 2 <= tm and n % (d * 2) == 0 and tm % (d * 2) == 0:
             d *= 2
         if d > 1 and C1 % 4 == 0:
-            second, s_second = (torch.zeros((B * n // d, C1), device=dev), 0, C1, C1, d), one
+            second, s_second = Seg(torch.zeros((B * n // d, C1), device=dev), 0, C1, C1, d), one
         else:
-            second, s_second = (Y, 0, C1, ld, 1), zero
-        both = Act([(Y, 0, C1, ld, 1), second], B * n, B, n,
+            second, s_second = Seg(Y, 0, C1, ld), zero
+        both = Act([Seg(Y, 0, C1, ld), second], B * n, B, n,
                    scale=torch.cat([one, s_second], 1).contiguous(),
                    shift=torch.cat([zero if f.shift is None else f.shift, zero], 1).contiguous(),
                    add=torch.cat([zero, g], 1).contiguous(), add_ld=2 * C1, post_relu=f.post_relu)
@@ -2405,10 +2443,10 @@ class FusedCloudConditionNet:
             mark("main:fp%d_done" % (i % (nlev + 1)))
         mapped = transfer(self.dec_map[0], 0, dec_cl, l_feat[0], V2=tables.get(id(self.dec_map[0])))
         Cm, Cf = mapped.shape[2], l_feat[0].shape[2]
-        head_in = Act([(mapped, 0, Cm, Cm, 1), (l_feat[0], 0, Cf, Cf, 1), (xyz4(xyz), 0, 3, 4, 1)], B * N, B, N)
-        Y, _, _, (s, t) = run_layer(head_in, self.head1, fold=FoldReq(self.head_norm, self.head1.Cout, N))
-        out, _, _ = run_layer(Act([(Y, 0, self.head1.Cout, Y.shape[1], 1)], B * N, B, N, scale=s, shift=t,
-                                  post_relu=True), self.head2)
+        head_in = Act([Seg(mapped, 0, Cm, Cm), Seg(l_feat[0], 0, Cf, Cf), Seg(xyz4(xyz), 0, 3, 4)], B * N, B, N)
+        lo = run_layer(head_in, self.head1, fold=FoldReq(self.head_norm, self.head1.Cout, N))
+        out = run_layer(act_from(lo, self.head1.Cout, B * N, B, N, scale=lo.folded[0], shift=lo.folded[1],
+                                 post_relu=True), self.head2).Y
         mark("main:head_done")
         eps = out.view(B, N, out.shape[1])[:, :, :self.head2.Cout]
         # (B, N, Cout) view over the layer's 4-float rows; samplers consume it in place (pdr_reverse_update reads a

@@ -36,7 +36,7 @@ def main():
             return mlp.chain(x2(), bank)
 
         def layers():
-            h2, _, _, _ = mlp(x2(), bank, relu_stats_extra=False)
+            h2, _ = mlp(x2(), bank, relu_stats_extra=False)
             return FN.materialize(h2)
         res = {}
         for label, fn in (("chain", chain), ("layers", layers)):

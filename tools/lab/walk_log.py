@@ -16,8 +16,8 @@ log = []
 def walk(self):
     r = orig(self)
     if self.P >= 262144:
-        segs = [(sg[2], "g" if len(sg) > 5 and sg[5] is not None else "p", sg[0].data_ptr() in FN._WALK) for sg in self.segs]
-        log.append((self.P, self.C, segs, None if self.radd is None else (self.radd[2], self.radd[0].data_ptr() in FN._WALK),
+        segs = [(sg.C, "g" if sg.gathered else "p", sg.t.data_ptr() in FN._WALK) for sg in self.segs]
+        log.append((self.P, self.C, segs, None if self.radd is None else (self.radd.C, self.radd.t.data_ptr() in FN._WALK),
                     self.dd is not None, r))
     return r
 

@@ -38,16 +38,15 @@ def instrument(records):
         act, conv = a[0], a[1]
         src_bytes = 0
         for sg in act.segs:
-            src_bytes += 4 * sg[2] * act.P // sg[4]
+            src_bytes += 4 * sg.C * act.P // sg.div
         if act.radd is not None:
             src_bytes += 4 * act.C * act.P
         def aligned(sg):
-            t, off, C, ld = sg[:4]
-            return (t.data_ptr() + 4 * off) % 16 == 0 and ld % 4 == 0 and ld >= (C + 3) // 4 * 4
+            return (sg.t.data_ptr() + 4 * sg.off) % 16 == 0 and sg.ld % 4 == 0 and sg.ld >= (sg.C + 3) // 4 * 4
         vec = all(aligned(sg) for sg in act.segs)
         if act.radd is not None:
             vec = vec and len(act.segs) == 1 and aligned(act.radd)
-        desc = "+".join("%d/%d%s" % (sg[2], sg[3], "" if aligned(sg) else "!") for sg in act.segs)
+        desc = "+".join("%d/%d%s" % (sg.C, sg.ld, "" if aligned(sg) else "!") for sg in act.segs)
         return dict(P=act.P, rpb=act.rpb, Cin=conv.Cin, Cout=conv.Cout, bytes=src_bytes + 4 * conv.Cout * act.P,
                     listed=act.dd is not None, gath=act.gidx is not None,
                     flops=2 * act.P * conv.Cin * conv.Cout, vec=vec, desc=desc + (" radd" if act.radd is not None else ""))
@@ -62,8 +61,8 @@ def instrument(records):
     split_call = FN.SplitFirstConv.__call__
     FN.SplitFirstConv.__call__ = wrap(
         "split_first", split_call,
-        lambda a, k, out: dict(P=out[0].shape[0], Cin=a[1].shape[2] + 9, Cout=a[0].Cout,
-                               bytes=8 * out[0].shape[0] * a[0].Cout, flops=0))
+        lambda a, k, out: dict(P=a[4].numel(), Cin=a[1].shape[2] + 9, Cout=a[0].Cout,
+                               bytes=8 * a[4].numel() * a[0].Cout, flops=0))
     fold = FN.Norm.fold
     FN.Norm.fold = wrap("gn_fold", fold, lambda a, k, out: dict(P=0, Cin=0, Cout=out[0].shape[1], bytes=0, flops=0))
 
