@@ -28,6 +28,7 @@ grouped block is split into per-point tables (SplitFirstConv), and a neighbourho
 `nsample` copies of one point is evaluated once (Dedup / SortedQueries: the per-neighbour launches walk only the
 128-row tiles that hold a real neighbourhood, a per-query chain of the same layers stands in for the rest).
 """
+import contextlib
 import ctypes
 from collections import namedtuple
 
@@ -84,11 +85,6 @@ STEP_TABLE = True
 # The global PointNet of a new batch (models/pnet.py) through the fused layer kernels (False: the torch module ->
 # MIOpen convolutions, what rounds 1-3 did)
 FUSE_GLOBAL_PNET = True
-# Lab probe (never changed in the product): LAB_SKIP_FOLD reuses every GroupNorm fold's first result -- wrong values,
-# right launches minus the folds: the 0.5 ms bound of DESIGN.md section 4.5.  (Stream priorities, measured in round 4:
-# the geometry stream or the blocks' second-half stream at HIP priority -1 beside normal-priority streams 11.5-12.0 ms
-# per step vs 8.75 -- kernels of different priorities no longer overlap; both at -1: 8.81-8.85; not used.)
-LAB_SKIP_FOLD = False
 # Neighbourhoods that are K copies of one row (ball_query pads with the first hit; a query with <= 1 point in its ball,
 # the rule on x_t for most of a reverse process) are evaluated ONCE: the per-neighbour launches of a grouped block walk
 # only the 128-row tiles that contain a real neighbourhood (pdr_dedup_plan), a per-QUERY chain of the same layers
@@ -453,6 +449,28 @@ class LayerOut:
         return iter((self.Y, self.stats.partial, self.stats.tpb))
 
 
+# What one half of a block hands to the other:
+# FusedAttention.values: the value conv's output, its folded GroupNorm, the per-query value rows of a deduplicated block
+Values = namedtuple("Values", "V scale shift twin")
+# EmbeddingBank.get: the (B, C) block of one registered Linear = columns [off, off + C) of `t` (leading dimension ld)
+Injected = namedtuple("Injected", "t off ld")
+# per-query first-conv tables [V | V0] made ahead of a block, and the query order they were made for (a SortedQueries;
+# None: the original order)
+QueryTables = namedtuple("QueryTables", "V2 order", defaults=(None,))
+# a grouped block behind its first conv (FusedGroupedBlock._head): sizes, the ball counts and the first conv in the
+# block's query order `sq` (a SortedQueries or None); rows: the row map of query features left in their original order.
+# query / q_ahead belong to the OTHER half -- the query features in the block's order and their query conv made ahead --
+# and are here only because the two-stream form issues both ahead of the first conv (the head is given the queries then)
+Head = namedtuple("Head", "B m K counts first folded sq rows query q_ahead", defaults=(None,) * 5)
+# FusedGroupedBlock.prepare: the head, the value half (a thunk) and the event behind both when another stream ran them
+Prepared = namedtuple("Prepared", "head values event", defaults=(None,))
+
+
+def _ready(x):
+    """The thunk form of a value that exists already (see _on_aux for one that another stream is still making)."""
+    return lambda: x
+
+
 def act_from(lo, C, P, B, rpb, **kw):
     """Act over the first C columns of a LayerOut, with its per-query twin when the layer ran deduplicated."""
     a = Act([Seg(lo.Y, 0, C, lo.Y.shape[1])], P, B, rpb, **kw)
@@ -525,19 +543,35 @@ def _pad4(c):
     return (c + 3) // 4 * 4
 
 
+# xyz4's cache entry: the source tensor, its padded copy, the stream that made the copy and an event behind it
+Padded = namedtuple("Padded", "src padded stream event")
 _XYZ4 = {}
 # Per-forward registry of what the geometry prepass made for a neighbour-index tensor (keyed by the tensor's id; the
-# entry holds the tensor, so the id cannot be reused within the forward): {"sorted": SortedQueries, "probed": bool}.
+# entry, a Geom, holds the tensor, so the id cannot be reused within the forward).
 # Cleared with _XYZ4 at the start of a forward.  (Rounds 4-5 hung these on the index tensors as attributes.)
 _GEOM = {}
 # per forward: data_ptr of a layer output -> the direction (0 forward / 1 reversed) its producer walked (ZIGZAG_WALK)
 _WALK = {}
 
 
+def _new_forward():
+    _XYZ4.clear()
+    _GEOM.clear()
+    _WALK.clear()
+
+
+class Geom:
+    """_GEOM's entry for the index tensor `tensor`: `sorted`, its SortedQueries once made; `probed`: its probe ran."""
+    __slots__ = ("tensor", "sorted", "probed")
+
+    def __init__(self, tensor):
+        self.tensor, self.sorted, self.probed = tensor, None, False
+
+
 def _geom(idx, create=False):
     e = _GEOM.get(id(idx))
     if e is None and create:
-        e = _GEOM[id(idx)] = {"tensor": idx, "sorted": None, "probed": False}
+        e = _GEOM[id(idx)] = Geom(idx)
     return e
 
 
@@ -569,13 +603,12 @@ def xyz4(t):
             cur = torch.cuda.current_stream(t.device)
             stream, ev = cur.cuda_stream, torch.cuda.Event()
             ev.record(cur)
-        hit = (t, padded, stream, ev)
-        _XYZ4[key] = hit
-    elif hit[3] is not None:
+        hit = _XYZ4[key] = Padded(t, padded, stream, ev)
+    elif hit.event is not None:
         cur = torch.cuda.current_stream(t.device)
-        if cur.cuda_stream != hit[2]:
-            cur.wait_event(hit[3])
-    return hit[1]
+        if cur.cuda_stream != hit.stream:
+            cur.wait_event(hit.event)
+    return hit.padded
 
 
 def plain(t2d, B, rows_per_batch, row_div=1, C=None):
@@ -657,6 +690,16 @@ def _on_aux(fn):
         main.wait_event(done)
         return result
     return join
+
+
+@contextlib.contextmanager
+def _single_stream():
+    """The blocks inside run both halves on the current stream (a half hoisted onto a stream that is busy anyway)."""
+    saved, _PAR["stream"] = _PAR["stream"], None
+    try:
+        yield
+    finally:
+        _PAR["stream"] = saved
 
 
 # Arithmetic of the wide GEMMs of the forward in flight: "f32" (exact fp32 MFMA, default) or "split_f16"
@@ -931,7 +974,6 @@ class Norm:
         gn = mod.group_norm if isinstance(mod, MyGroupNorm) else mod
         self.G, self.Cn, self.eps = gn.num_groups, gn.num_channels, gn.eps
         self.gamma, self.beta = gn.weight.detach().contiguous(), gn.bias.detach().contiguous()
-        self._lab_fold = {}            # LAB_SKIP_FOLD: (B, C, n) -> the first result of that fold
 
     def fold(self, parts, B, C, n):
         """parts: one or two Window (Stats.window; or their fields as plain tuples) covering C channels in order.
@@ -940,10 +982,6 @@ class Norm:
         dev = self.gamma.device
         parts = [Window(*p) for p in parts]
         assert 1 <= len(parts) <= 2 and sum(p.C for p in parts) == C
-        if LAB_SKIP_FOLD and (B, C, n) in self._lab_fold:
-            # lab probe (never set in the product): the fold of a call site runs ONCE, later calls reuse its result --
-            # wrong values, right shapes: an upper bound on what taking the fold launches out of the step could buy
-            return self._lab_fold[(B, C, n)]
         scale = torch.empty((B, C), dtype=torch.float32, device=dev)
         shift = torch.empty((B, C), dtype=torch.float32, device=dev)
 
@@ -958,8 +996,6 @@ class Norm:
         _lib.check(lib.pdr_gn_fold(*window(a), *window(b), B, self.Cn, self.G, float(n), float(self.eps),
                                    self.gamma.data_ptr(), self.beta.data_ptr(), scale.data_ptr(), shift.data_ptr(),
                                    *sub(a), *sub(b), _stream()), "gn_fold")
-        if LAB_SKIP_FOLD:
-            self._lab_fold[(B, C, n)] = (scale, shift)
         return scale, shift
 
 
@@ -1001,10 +1037,6 @@ class EmbeddingBank:
                     o += m.weight.shape[0]
                 self.offs[k] = offs
 
-    def evaluate(self, t_emb, c_emb, c2_emb):
-        src = {"t": t_emb, "c": c_emb, "c2": c2_emb}
-        self.out = {k: F.linear(src[k], self.W[k], self.b[k]) for k in self.W}
-
     def evaluate_kind(self, kind, src, static=False):
         """One embedding kind.  static=True: the result is written IN PLACE into the buffer of the previous call
         (same shape), so that a captured hipGraph -- which does not contain this GEMM -- keeps reading a valid
@@ -1033,12 +1065,12 @@ class EmbeddingBank:
             self.out[kind] = val
 
     def get(self, handle):
-        """(tensor, offset, ld) of the (B, C) block of `handle`."""
+        """Injected (tensor, offset, ld) of the (B, C) block of `handle`."""
         if handle is None:
             return None
         k, i = handle
         o, n = self.offs[k][i]
-        return self.out[k], o, self.out[k].shape[1]
+        return Injected(self.out[k], o, self.out[k].shape[1])
 
 
 class FusedMlp:
@@ -1080,7 +1112,8 @@ class FusedMlp:
         `first` holds the [first conv | res conv | extra convs] columns and their statistics."""
         relu0 = self.extra_col0 if relu_stats_extra else None
         lo = run_layer(x, self.first, relu_col0=relu0, fold=self.first_fold(x.rpb))
-        return self.after_first(FirstOut(Y=lo.Y, stats=lo.stats), x.P, x.B, x.rpb, bank, x, folded=lo.folded)
+        first = FirstOut(Y=lo.Y, stats=lo.stats)
+        return self.after_first(first, x.P, x.B, x.rpb, bank, x, folded=_ready(lo.folded))
 
     def chain(self, x, bank):
         """The whole MLP on per-point rows as ONE pdr_point_chain launch -> (P, Clast) tensor, or None when the shapes
@@ -1108,10 +1141,10 @@ class FusedMlp:
             L.relu_pre, L.relu_post = 0, 1
             inj = bank.get(self.inject.get(i))
             if inj is not None:
-                if inj[1] % 4 != 0:
+                if inj.off % 4 != 0:
                     return None
-                L.add, L.add_ld = _ptr(inj[0], inj[1]), inj[2]
-                keep.append(inj[0])
+                L.add, L.add_ld = _ptr(inj.t, inj.off), inj.ld
+                keep.append(inj.t)
         ch.residual = 1 if self.res_col0 is not None else 0
         plan = (ctypes.c_long * 4)()
         if lib.pdr_point_chain_plan(ctypes.byref(ch), B, n, plan) != _lib.PDR_OK:
@@ -1134,21 +1167,25 @@ class FusedMlp:
         """Fold request of the GroupNorm behind the first conv (for whoever launches that conv)."""
         return FoldReq(self.norms[0], self.C1, rpb)
 
+    def first_conv_args(self, rpb):
+        """What a SplitFirstConv that stands for this MLP's first conv is called with: the residual conv's column
+        window and the first GroupNorm's fold request."""
+        return dict(res=(self.res_col0, self.Clast) if self.res_col0 is not None else None, fold=self.first_fold(rpb))
+
     def after_first(self, first, P, B, rpb, bank, x=None, folded=None):
-        """Everything behind the first conv, given its output and statistics (`first`, a FirstOut) and, when the first
-        conv's launch carried it, the fold of the first GroupNorm (`folded` = (scale, shift), or a thunk launching it).
-        Returns (h, first)."""
+        """Everything behind the first conv, given its output and statistics (`first`, a FirstOut) and, when whoever
+        launched the first conv made or requested it, the fold of the first GroupNorm (`folded`: a thunk yielding
+        (scale, shift), called here, on the stream that runs the rest of the MLP).  Returns (h, first)."""
         stats = first.stats
         cur = first.attach(Act([first.seg(0, self.C1)], P, B, rpb))
-        if callable(folded):
-            folded = folded()
+        folded = folded() if folded is not None else None
         for i, norm in enumerate(self.norms):
             C = cur.C
             scale, shift = folded if folded is not None else norm.fold([stats.window(0, C)], B, C, rpb)
             cur.scale, cur.shift, cur.post_relu = scale, shift, True
             inj = bank.get(self.inject.get(i))
             if inj is not None:
-                cur.add, cur.add_ld = inj[0][:, inj[1]:], inj[2]
+                cur.add, cur.add_ld = inj.t[:, inj.off:], inj.ld
             if i < len(self.rest):
                 lo = run_layer(cur, self.rest[i], fold=FoldReq(self.norms[i + 1], self.rest[i].Cout, rpb))
                 stats, folded = lo.stats, lo.folded
@@ -1191,21 +1228,23 @@ class FusedAttention:
         self.D = self.w2.Cout
 
     def values(self, h, B, npoint, K):
-        """Value half (independent of the query features): value conv + its GroupNorm fold -> (V, scale, shift, twin);
-        twin: the per-query value rows of a deduplicated block.  (Not the LayerOut: its statistics are done with.)"""
+        """Value half (independent of the query features): value conv + its GroupNorm fold -> Values (V, scale, shift,
+        twin); twin: the per-query value rows of a deduplicated block.  (Not the LayerOut: its statistics are done
+        with.)"""
         lo = run_layer(h, self.v, fold=FoldReq(self.v_norm, self.D, npoint * K) if self.v_norm is not None else None)
-        return (lo.Y, *(lo.folded or (None, None)), lo.twin)
+        return Values(lo.Y, *(lo.folded or (None, None)), lo.twin)
 
     def query_conv(self, query, B, npoint):
         """The query conv and its statistics (the first launch of __call__), for callers that issue it ahead."""
         return run_layer(plain(query, B, npoint), self.q, stats=True, relu_col0=0)
 
-    def __call__(self, query, h, first, key_col0, counts, B, npoint, K, values=None, sorted_q=None,
-                 query_rows=None, q_ahead=None):
-        """query: (B*npoint, Cq) tensor; h: Act (value input); key = columns [key_col0, key_col0 + C2) of the block's
-        first conv `first` (a FirstOut: output + statistics);
-        values: result of self.values(h, ...) when it was evaluated ahead of time.
-        q_ahead: the LayerOut of query_conv (or a thunk yielding it) when the query conv was launched ahead.
+    def __call__(self, query, first, key_col0, counts, B, npoint, K, values, sorted_q=None, query_rows=None,
+                 q_ahead=None):
+        """query: (B*npoint, Cq) tensor; key = columns [key_col0, key_col0 + C2) of the block's first conv `first` (a
+        FirstOut: output + statistics);
+        values: a thunk yielding the Values of self.values(h, ...), called where the pooling needs them: it launches
+        the value half there, or joins the stream that runs it (_on_aux), or hands over what exists (_ready).
+        q_ahead: a thunk of the same kinds yielding the LayerOut of query_conv when that conv was launched ahead.
         query_rows: int32 (B*npoint) -- `query` is in another row order than the block's positions (QUERIES_IN_PLACE:
         the original order of a block evaluated on sorted queries): position p's query is row query_rows[p / K]."""
         lib = _lib.load()
@@ -1216,7 +1255,7 @@ class FusedAttention:
         n1_fold = FoldReq(self.n1, self.C1, npoint * K, mult0=float(K),
                           second=first.stats.window(key_col0, self.C2))
         if q_ahead is not None:                      # the query conv was launched ahead (query_conv): join, then fold
-            ql = q_ahead() if callable(q_ahead) else q_ahead
+            ql = q_ahead()
             s, t = n1_fold.launch(ql.stats, B)
         else:
             ql = run_layer(plain(query, B, npoint), self.q, relu_col0=0, fold=n1_fold)
@@ -1250,9 +1289,7 @@ class FusedAttention:
         # at its ORIGINAL place (out_rows); the unfused fallback below pools in sorted order and gathers back
         fused_pool = FUSE_SCORE_POOL and K in (8, 16, 32) and (npoint * K) % 32 == 0 and self.D % 4 == 0
         out_rows = sorted_q.perm_rows if (sorted_q is not None and dd is not None and fused_pool) else None
-        # (a callable: the value half runs on another stream; calling it joins that stream into this one)
-        V, vs, vt, Vtwin = values() if callable(values) else \
-            (values if values is not None else self.values(h, B, npoint, K))
+        V, vs, vt, Vtwin = values()                  # (the value half ran on another stream: this joins it)
         mark("  blk:joined", True)
         out = torch.empty((B * npoint, self.D), dtype=torch.float32, device=V.device)
         cptr = counts.data_ptr() if counts is not None else None
@@ -1629,7 +1666,7 @@ class FusedGroupedBlock:
     def _sorted(self, idx):
         """The SortedQueries made for this index tensor, when this block evaluates its queries in that order."""
         e = _geom(idx)
-        return e["sorted"] if (e is not None and _dedup_on() and self.dedup) else None
+        return e.sorted if (e is not None and _dedup_on() and self.dedup) else None
 
     def plan_ahead(self, neigh, new_xyz):
         """On the CURRENT stream (the one that produced `neigh`), ahead of the block: the query order and the plan --
@@ -1638,25 +1675,17 @@ class FusedGroupedBlock:
         B, m, K = idx.shape
         e = _geom(idx, create=True)
         if self._eligible(idx, m, K):
-            if e["sorted"] is None:
-                e["sorted"] = SortedQueries(idx, counts, new_xyz)      # (with the plan of the sorted arrays)
-        elif _PROBE[0] is not None and self._shape_ok(idx, m, K) and not e["probed"]:
+            if e.sorted is None:
+                e.sorted = SortedQueries(idx, counts, new_xyz)      # (with the plan of the sorted arrays)
+        elif _PROBE[0] is not None and self._shape_ok(idx, m, K) and not e.probed:
             _lib.check(_lib.load().pdr_dedup_probe(counts.data_ptr(), B, m, K, _probe_ptr(), _stream()), "dedup_probe")
-            e["probed"] = True
+            e.probed = True
         return neigh
 
     def side_tables(self, neigh, new_xyz, has_v0):
-        """Per-query tables of the first conv, for the query order the block will use: (tables, that order)."""
+        """Per-query tables of the first conv, for the query order the block will use -> QueryTables."""
         sq = self._sorted(neigh[0])
-        return self.split.query_tables(sq.xyz if sq is not None else new_xyz, has_v0=has_v0), sq
-
-    @staticmethod
-    def _tables_for(V2, sq):
-        """The per-query tables a caller handed over, if they were made for THIS query order (side_tables' pair; a bare
-        tensor = made for the original order), else None: the block evaluates them itself."""
-        if isinstance(V2, tuple):
-            return V2[0] if V2[1] is sq else None
-        return V2 if sq is None else None
+        return QueryTables(self.split.query_tables(sq.xyz if sq is not None else new_xyz, has_v0=has_v0), sq)
 
     def _make_split(self, Cs):
         if self.split is None:
@@ -1684,97 +1713,90 @@ class FusedGroupedBlock:
     def neighbours(self, src_xyz, new_xyz):
         return _ext.ball_query(new_xyz, src_xyz, self.radius, self.nsample)
 
-    def query_tables(self, src_feat_width, new_xyz, subset):
-        """Per-query tables of the first conv for queries `new_xyz` (needs coordinates only): lets the caller issue
-        these small launches early.  None when the split first conv is off."""
-        if not USE_SPLIT_FIRST:
-            return None
-        return self._make_split(src_feat_width).query_tables(new_xyz, has_v0=not subset)
+    @staticmethod
+    def _ordered(query_feats_cl, sq, rows):
+        """The query features as the attention reads them: gathered into the block's sorted order unless it reads them
+        through the row map `rows`."""
+        return gather_rows(query_feats_cl, sq.perm) if (sq is not None and rows is None) else query_feats_cl
+
+    def _head(self, src_xyz, src_feats_cl, new_xyz, subset, neigh, tables, U=None, query=None, q_ahead=None):
+        """The block up to and including its first conv (USE_SPLIT_FIRST) -> Head: the neighbours, the switch to the
+        sorted query order, the per-query tables `tables` (a QueryTables) if they were made for that order -- else the
+        first conv evaluates them --, the first conv's statistics pass.  query: the block's query features, when the
+        caller has them already: put into the block's order here, ahead of the first conv, and their query conv goes
+        ahead on the second stream unless `q_ahead` (made on the ORIGINAL query order) still serves."""
+        B, m, _ = new_xyz.shape
+        K = self.nsample
+        idx, counts = neigh if neigh is not None else self.neighbours(src_xyz, new_xyz)
+        sq, rows = self._sorted(idx), None
+        if sq is not None:                     # the block's queries in sorted order (the pooling puts the output back)
+            idx, counts, new_xyz = sq.idx, sq.counts, sq.xyz
+            rows = sq.perm_rows if self._in_place(K) else None
+        if query is not None:
+            query = self._ordered(query, sq, rows)
+            if q_ahead is not None and not (sq is None or rows is not None):
+                q_ahead = None                 # (made on the original order, but this block gathered its queries)
+            if q_ahead is None and QUERY_CONV_AHEAD and SPLIT_QUERY_CONV:
+                qf = query.reshape(B * m, -1)
+                q_ahead = _on_aux(lambda: self.att.query_conv(qf, B, m))
+        first, folded = self._make_split(src_feats_cl.shape[2])(
+            src_feats_cl, src_xyz, new_xyz, idx, None if subset else counts, K, self.mlp.extra_col0,
+            virtual=USE_VIRTUAL_FIRST, U=U if U is not None else self.static_U,
+            V2=tables.V2 if (tables is not None and tables.order is sq) else None,
+            dd=self._plan(idx, counts, B, m, K, sq), **self.mlp.first_conv_args(m * K))
+        return Head(B, m, K, counts, first, folded, sq, rows, query, q_ahead)
+
+    def _values(self, hd, bank):
+        """The half that does not involve the query features, behind the head: shared MLP + value half -> Values."""
+        h, _ = self.mlp.after_first(hd.first, hd.B * hd.m * hd.K, hd.B, hd.m * hd.K, bank, folded=hd.folded)
+        return self.att.values(h, hd.B, hd.m, hd.K)
+
+    def _pool(self, hd, query_feats_cl, values, q_ahead=None):
+        """The query / score / pooling half -> (B, m, D), rows in the original query order (see FusedAttention)."""
+        out = self.att(query_feats_cl.reshape(hd.B * hd.m, -1), hd.first, self.mlp.extra_col0, hd.counts, hd.B, hd.m,
+                       hd.K, values, sorted_q=hd.sq, query_rows=hd.rows, q_ahead=q_ahead)
+        return out.view(hd.B, hd.m, -1)
 
     def prepare(self, src_xyz, src_feats_cl, new_xyz, bank, subset, neigh=None, V2=None):
         """Everything that does not involve the QUERY features: grouping, the shared MLP and the value half of the
-        attention.  For the feature-transfer blocks this depends on coordinates and static tables only, so it can
-        run ahead of the feature path on another stream."""
+        attention -> Prepared.  For the feature-transfer blocks this depends on coordinates and static tables only, so
+        it can run ahead of the feature path on another stream."""
+        if USE_SPLIT_FIRST:
+            hd = self._head(src_xyz, src_feats_cl, new_xyz, subset, neigh, V2)
+            return Prepared(hd, _ready(self._values(hd, bank)))
         B, m, _ = new_xyz.shape
         idx, counts = neigh if neigh is not None else self.neighbours(src_xyz, new_xyz)
         K = self.nsample
-        sq = self._sorted(idx) if USE_SPLIT_FIRST else None
-        if sq is not None:                     # the block's queries in sorted order (finish() puts the output back)
-            idx, counts, new_xyz = sq.idx, sq.counts, sq.xyz
-        V2 = self._tables_for(V2, sq)          # (tables of another query order: evaluated here instead)
-        if USE_SPLIT_FIRST:
-            split = self._make_split(src_feats_cl.shape[2])
-            first, folded = split(src_feats_cl, src_xyz, new_xyz, idx, None if subset else counts, K,
-                                  self.mlp.extra_col0, virtual=USE_VIRTUAL_FIRST,
-                                  res=(self.mlp.res_col0, self.mlp.Clast) if self.mlp.res_col0 is not None else None,
-                                  U=self.static_U, V2=V2, fold=self.mlp.first_fold(m * K),
-                                  dd=self._plan(idx, counts, B, m, K, sq))
-            h, first = self.mlp.after_first(first, B * m * K, B, m * K, bank, folded=folded)
-        else:
-            dense_feats = src_feats_cl.dense() if isinstance(src_feats_cl, Cat) else src_feats_cl
-            G, Cg = group_build(dense_feats, src_xyz, new_xyz, idx, counts, not subset, self.with_abs,
-                                self.with_centre)
-            h, first = self.mlp(plain(G, B, m * K, C=Cg), bank)
-        return dict(h=h, first=first, counts=counts, B=B, m=m, K=K, sq=sq, values=self.att.values(h, B, m, K))
+        dense_feats = src_feats_cl.dense() if isinstance(src_feats_cl, Cat) else src_feats_cl
+        G, Cg = group_build(dense_feats, src_xyz, new_xyz, idx, counts, not subset, self.with_abs, self.with_centre)
+        h, first = self.mlp(plain(G, B, m * K, C=Cg), bank)
+        return Prepared(Head(B, m, K, counts, first), _ready(self.att.values(h, B, m, K)))
 
     def finish(self, prep, query_feats_cl):
-        B, m, K, sq = prep["B"], prep["m"], prep["K"], prep["sq"]
-        rows = None
-        if sq is not None:
-            if self._in_place(K):
-                rows = sq.perm_rows
-            else:
-                query_feats_cl = gather_rows(query_feats_cl, sq.perm)
-        out = self.att(query_feats_cl.reshape(B * m, -1), prep["h"], prep["first"], self.mlp.extra_col0,
-                       prep["counts"], B, m, K, values=prep["values"], sorted_q=sq, query_rows=rows)
-        return out.view(B, m, -1)                 # (rows in the original query order, see FusedAttention)
+        hd = prep.head
+        return self._pool(hd, self._ordered(query_feats_cl, hd.sq, hd.rows), prep.values)
 
     def __call__(self, src_xyz, src_feats_cl, new_xyz, query_feats_cl, bank, subset, neigh=None, V2=None, U=None,
                  q_ahead=None):
-        """U: the per-source table of the first conv (SplitFirstConv.source_table) when the caller made it ahead of
-        time -- it needs the source cloud only, not the queries.  q_ahead: the attention's query conv when the caller
-        launched it ahead (FusedAttention.query_conv on the ORIGINAL query order: QUERIES_IN_PLACE)."""
-        B, m, _ = new_xyz.shape
-        K = self.nsample
+        """V2: the QueryTables made ahead for this block, if any.  U: the per-source table of the first conv
+        (SplitFirstConv.source_table) when the caller made it ahead of time -- it needs the source cloud only, not the
+        queries.  q_ahead: a thunk yielding the attention's query conv when the caller launched it ahead
+        (FusedAttention.query_conv on the ORIGINAL query order: QUERIES_IN_PLACE)."""
         if not (USE_SPLIT_FIRST and _PAR["stream"] is not None):
             return self.finish(self.prepare(src_xyz, src_feats_cl, new_xyz, bank, subset, neigh, V2=V2),
                                query_feats_cl)
-        # deep level: first GEMM here, then [MLP + value conv] on the auxiliary stream beside [query / score convs]
-        idx, counts = neigh if neigh is not None else self.neighbours(src_xyz, new_xyz)
-        sq = self._sorted(idx)
-        rows = None
-        if sq is not None:                     # the block's queries in sorted order; its output is put back below
-            idx, counts, new_xyz = sq.idx, sq.counts, sq.xyz
-            if self._in_place(K):
-                rows = sq.perm_rows
-            else:
-                query_feats_cl = gather_rows(query_feats_cl, sq.perm)
-        V2 = self._tables_for(V2, sq)          # (tables of another query order: evaluated in the block instead)
-        if q_ahead is not None and not (sq is None or rows is not None):
-            q_ahead = None                     # (made on the original order, but this block gathered its queries)
-        if q_ahead is None and QUERY_CONV_AHEAD and SPLIT_QUERY_CONV:
-            qf = query_feats_cl.reshape(B * m, -1)
-            q_ahead = _on_aux(lambda: self.att.query_conv(qf, B, m))
-        split = self._make_split(src_feats_cl.shape[2])
-        first, folded = split(src_feats_cl, src_xyz, new_xyz, idx, None if subset else counts, K,
-                              self.mlp.extra_col0, virtual=USE_VIRTUAL_FIRST,
-                              res=(self.mlp.res_col0, self.mlp.Clast) if self.mlp.res_col0 is not None else None,
-                              U=U if U is not None else self.static_U, V2=V2, fold=self.mlp.first_fold(m * K),
-                              dd=self._plan(idx, counts, B, m, K, sq))
-
+        # first conv here, then [MLP + value conv] on the auxiliary stream beside [query / score convs]
+        hd = self._head(src_xyz, src_feats_cl, new_xyz, subset, neigh, V2, U, query_feats_cl, q_ahead)
         mark("  blk:first_conv_stats_done", True)
 
-        def chain_a():
+        def value_half():
             mark("  blk:aux_begin", True)
-            h, _ = self.mlp.after_first(first, B * m * K, B, m * K, bank, folded=folded)
-            r = self.att.values(h, B, m, K)
+            r = self._values(hd, bank)
             mark("  blk:aux_values_done", True)
             return r
-        values = _on_aux(chain_a)
-        out = self.att(query_feats_cl.reshape(B * m, -1), None, first, self.mlp.extra_col0, counts, B, m, K,
-                       values=values, sorted_q=sq, query_rows=rows, q_ahead=q_ahead)
+        out = self._pool(hd, hd.query, _on_aux(value_half), hd.q_ahead)
         mark("  blk:pool_done", True)
-        return out.view(B, m, -1)                 # (rows in the original query order, see FusedAttention)
+        return out
 
 
 class FusedKnnFP:
@@ -1806,20 +1828,18 @@ class FusedKnnFP:
             qf = unknown_feats_cl.reshape(B * n, -1)
             q_ahead = _on_aux(lambda: self.att.query_conv(qf, B, n))
         if USE_SPLIT_FIRST:
-            self._make_split(C)
-            first, folded = self.split(
-                known_feats_cl, known, unknown, idx, None, K, self.mlp1.extra_col0, s1=d2, s2=wgt, V2=V2, U=U,
-                virtual=USE_VIRTUAL_FIRST and USE_VIRTUAL_KNN,
-                res=(self.mlp1.res_col0, self.mlp1.Clast) if self.mlp1.res_col0 is not None else None,
-                fold=self.mlp1.first_fold(n * K))
+            first, folded = self._make_split(C)(
+                known_feats_cl, known, unknown, idx, None, K, self.mlp1.extra_col0, s1=d2, s2=wgt,
+                V2=V2.V2 if V2 is not None else None, U=U, virtual=USE_VIRTUAL_FIRST and USE_VIRTUAL_KNN,
+                **self.mlp1.first_conv_args(n * K))
+
+            def mlp():
+                return self.mlp1.after_first(first, B * n * K, B, n * K, bank, folded=folded)[0]
             if _PAR["stream"] is not None:
-                def chain_a():
-                    hh, _ = self.mlp1.after_first(first, B * n * K, B, n * K, bank, folded=folded)
-                    return self.att.values(hh, B, n, K)
-                h, values = None, _on_aux(chain_a)
+                values = _on_aux(lambda: self.att.values(mlp(), B, n, K))
             else:
-                h, first = self.mlp1.after_first(first, B * n * K, B, n * K, bank, folded=folded)
-                values = None
+                h = mlp()
+                values = lambda: self.att.values(h, B, n, K)        # (one stream: launched where the pooling needs it)
         else:
             G = torch.empty((B * n * K, _pad4(C + 11)), dtype=torch.float32, device=unknown.device)
             idx64 = idx.long()
@@ -1828,9 +1848,9 @@ class FusedKnnFP:
                                          idx64.data_ptr(), d2.data_ptr(), B, n, n2, K, G.data_ptr(), G.shape[1],
                                          _stream()), "knn_build")
             h, first = self.mlp1(plain(G, B, n * K, C=C + 11), bank)
-            values = None
-        interp = self.att(unknown_feats_cl.reshape(B * n, -1), h, first, self.mlp1.extra_col0, None, B, n, K,
-                          values=values, q_ahead=q_ahead)
+            values = lambda: self.att.values(h, B, n, K)
+        interp = self.att(unknown_feats_cl.reshape(B * n, -1), first, self.mlp1.extra_col0, None, B, n, K, values,
+                          q_ahead=q_ahead)
         Cs = unknown_feats_cl.shape[2]
         x2 = Act([Seg(interp, 0, self.att.D, interp.shape[1]), Seg(xyz4(unknown_feats_cl), 0, Cs, _pad4(Cs)),
                   Seg(xyz4(unknown), 0, 3, 4)], B * n, B, n)
@@ -1982,7 +2002,7 @@ class FusedCloudConditionNet:
             self.global_pnet = None              # (outside the fused family: the torch module computes it)
         self.enc_cl = self.dec_cl = None
         self._synced = False
-        self._side = None
+        self._streams = {"side": None, "fps": None, "aux": None}     # created on first use (_stream_named)
         self.return_strided_eps = False
         self.two_streams = True       # the two halves of every block on two streams (False: profiling tools that want
         self._label_key = None        # every kernel alone on the chip)
@@ -1997,20 +2017,11 @@ class FusedCloudConditionNet:
         # set by a sampler (build_step_table); the step's embedding chain is then ONE row lookup (pdr_embed_select)
         self.step_table = None
 
-    def _side_stream(self):
-        if self._side is None:
-            self._side = torch.cuda.Stream(device=next(self.net.parameters()).device)
-        return self._side
-
-    def _fps_stream(self):
-        if getattr(self, "_fps", None) is None:
-            self._fps = torch.cuda.Stream(device=next(self.net.parameters()).device)
-        return self._fps
-
-    def _aux_stream(self):
-        if getattr(self, "_aux", None) is None:
-            self._aux = torch.cuda.Stream(device=next(self.net.parameters()).device)
-        return self._aux
+    def _stream_named(self, name):
+        """The geometry ("side"), sampling ("fps") or block-halves ("aux") stream of this network."""
+        if self._streams[name] is None:
+            self._streams[name] = torch.cuda.Stream(device=next(self.net.parameters()).device)
+        return self._streams[name]
 
     def sync_condition(self):
         """Channel-last copies of the retained condition features.  Called once per batch, after the
@@ -2033,9 +2044,7 @@ class FusedCloudConditionNet:
         # the feature-transfer blocks read these static clouds as their SOURCE: the per-source half of their
         # first conv (SplitFirstConv.source_table) is evaluated here, once per batch, not once per step
         with torch.no_grad():
-            _XYZ4.clear()
-            _GEOM.clear()
-            _WALK.clear()
+            _new_forward()
             for i, blk in enumerate(self.enc_map):
                 blk.prepare_static_source(net.l_uvw[i], self.enc_cl[i])
             for i, blk in enumerate(self.dec_map):
@@ -2094,12 +2103,10 @@ class FusedCloudConditionNet:
         saved = _PRECISION[0], _NET_DEDUP[0], _PROBE[0]
         _PRECISION[0], _NET_DEDUP[0], _PROBE[0] = self.precision, bool(self.dedup), self.probe
         saved_par = _PAR["stream"]
-        _PAR["stream"] = self._aux_stream() if self.two_streams else None
+        _PAR["stream"] = self._stream_named("aux") if self.two_streams else None
         try:
             if fresh:
-                _XYZ4.clear()
-                _GEOM.clear()
-                _WALK.clear()
+                _new_forward()
                 self._condition_branch(condition)
             return self._forward_cached(pointcloud, condition, ts, label)
         finally:
@@ -2203,9 +2210,7 @@ class FusedCloudConditionNet:
     def _forward_cached(self, pointcloud, condition, ts, label):
         net, hp, bank = self.net, self.net.hparams, self.bank
         B, N, _ = pointcloud.shape
-        _XYZ4.clear()
-        _GEOM.clear()
-        _WALK.clear()
+        _new_forward()
         mark("step:begin")
         xyz = pointcloud[:, :, 0:3].contiguous()
         # scale_factor == 1 (checked at construction): xyz / 1 is xyz, bit for bit -- no division kernel, and the
@@ -2225,14 +2230,14 @@ class FusedCloudConditionNet:
         # The encoder and decoder feature-transfer modules of one level query the SAME clouds with the same radius /
         # nsample (shipped configs): that ball query is computed once and shared.
         main = torch.cuda.current_stream()
-        side = self._side_stream()
+        side = self._stream_named("side")
         # (both placements pay only while the blocks' launches are small -- one-point neighbourhoods evaluated once; with
         # every neighbourhood evaluated the main stream has no idle window and the sampling chain competes with full
         # kernels: same box, whole form, 9.33 / 9.34 ms per step with both, 8.78 without the level-0 hoist on the main
         # stream, 8.70 / 8.72 without either)
         fps_on = FPS_STREAM and _dedup_on()
         hoist0_main = HOIST_LEVEL0_ON_MAIN and _dedup_on()
-        fps_s = self._fps_stream() if fps_on else side
+        fps_s = self._stream_named("fps") if fps_on else side
         xyz4(xyz)                                   # (read by all three streams: produced ahead of the fork)
         side.wait_stream(main)
         fps_s.wait_stream(main)
@@ -2299,10 +2304,10 @@ class FusedCloudConditionNet:
         ev_emb = event(main)
 
         def transfer(blk, l, cl, query, V2=None, q_ahead=None):
-            if id(blk) in prepared:
-                prep, ev = prepared[id(blk)]
-                if ev is not None:
-                    main.wait_event(ev)
+            prep = prepared.get(id(blk))
+            if prep is not None:
+                if prep.event is not None:
+                    main.wait_event(prep.event)
                 return blk.finish(prep, query)
             return blk(l_uvw[l], cl[l], l_xyz[l], query, bank, subset=False, neigh=fm_neigh[fm_key(l, blk)], V2=V2,
                        q_ahead=q_ahead)
@@ -2310,40 +2315,24 @@ class FusedCloudConditionNet:
         prepared = {}
         hoist = AHEAD_DECODER_MAPS and USE_SPLIT_FIRST and self.two_streams
         hoisted = [False]
+        hoist_enc = AHEAD_ENCODER_MAPS and hoist and (_dedup_on() or AHEAD_ENCODER_MAPS_WHOLE)
 
-        def hoist_decoder_map(l):
-            """side stream: the query-independent half of the decoder's feature-transfer block of level l (first-conv
-            statistics, shared MLP, value conv: coordinates, static condition features and embeddings only)."""
-            blk = self.dec_map[l]
-            if not hoist or tables.get(id(blk)) is None:
+        def hoist_map(blk, cl, l):
+            """side stream: the query-independent half of a feature-transfer block of level l (first-conv statistics,
+            shared MLP, value conv: coordinates, static condition features `cl` and embeddings only).  The decoder's
+            blocks once the geometry is done; the encoder's right behind level l's neighbourhoods (see FPS_STREAM on
+            when hoists pay)."""
+            if tables.get(id(blk)) is None:
                 # (no per-query tables made on the geometry stream: the block runs whole on the main stream)
                 return
             with torch.cuda.stream(side):
                 if not hoisted[0]:
                     side.wait_event(ev_emb)                 # the blocks' MLPs add the step / condition embeddings
                     hoisted[0] = True
-                saved_par, _PAR["stream"] = _PAR["stream"], None
-                prep = blk.prepare(l_uvw[l], dec_cl[l], l_xyz[l], bank, subset=False,
-                                   neigh=fm_neigh[fm_key(l, blk)], V2=tables.get(id(blk)))
-                _PAR["stream"] = saved_par
-                prepared[id(blk)] = (prep, event(side))
-
-        def hoist_encoder_map(l):
-            """side stream, right behind level l's neighbourhoods: the query-independent half of the encoder's
-            feature-transfer block of level l (deduplicated form only: see FPS_STREAM on when hoists pay)."""
-            blk = self.enc_map[l]
-            if not (AHEAD_ENCODER_MAPS and hoist and (_dedup_on() or AHEAD_ENCODER_MAPS_WHOLE)) or \
-                    tables.get(id(blk)) is None:
-                return
-            with torch.cuda.stream(side):
-                if not hoisted[0]:
-                    side.wait_event(ev_emb)
-                    hoisted[0] = True
-                saved_par, _PAR["stream"] = _PAR["stream"], None
-                prep = blk.prepare(l_uvw[l], enc_cl[l], l_xyz[l], bank, subset=False,
-                                   neigh=fm_neigh[fm_key(l, blk)], V2=tables.get(id(blk)))
-                _PAR["stream"] = saved_par
-                prepared[id(blk)] = (prep, event(side))
+                with _single_stream():
+                    prep = blk.prepare(l_uvw[l], cl[l], l_xyz[l], bank, subset=False, neigh=fm_neigh[fm_key(l, blk)],
+                                       V2=tables[id(blk)])
+                prepared[id(blk)] = prep._replace(event=event(side))
 
         def geometry_tail():
             """side stream, behind the last level's groupings: the remaining per-query tables and the kNN searches (first
@@ -2355,8 +2344,9 @@ class FusedCloudConditionNet:
                         tables[id(self.dec_map[0])] = self.dec_map[0].side_tables(fm_neigh[fm_key(0, self.dec_map[0])],
                                                                                   l_xyz[0], True)
                     for i in range(-1, -(len(self.fp) + 1), -1):
-                        if self.fp[i].split is not None:
-                            tables[id(self.fp[i])] = self.fp[i].split.query_tables(l_xyz[i - 1], has_v0=False)
+                        fp = self.fp[i]
+                        if fp.split is not None:
+                            tables[id(fp)] = QueryTables(fp.split.query_tables(l_xyz[i - 1], has_v0=False))
                 for i in range(-1, -(len(self.fp) + 1), -1):
                     knn[i] = _ext.knn_group(l_xyz[i - 1], l_xyz[i], self.fp[i].K)
                 mark("side:knn_done")
@@ -2368,8 +2358,8 @@ class FusedCloudConditionNet:
             group_level(k)
             lv = k + 1
             transfer_level(lv, (self.enc_map[lv],) if lv < nlev else (self.dec_map[lv],))
-            if lv < nlev:
-                hoist_encoder_map(lv)
+            if lv < nlev and hoist_enc:
+                hoist_map(self.enc_map[lv], enc_cl, lv)
         if side_tables_on:
             # the decoder's transfer blocks of the inner levels share the encoder's neighbourhoods: their tables
             with torch.cuda.stream(side):
@@ -2378,8 +2368,9 @@ class FusedCloudConditionNet:
                     if blk.split is not None and id(blk) not in tables:
                         tables[id(blk)] = blk.side_tables(fm_neigh[fm_key(l, blk)], l_xyz[l], True)
         ev_knn = geometry_tail()
-        for l in range(nlev, 0 if hoist0_main else -1, -1):   # in the order the decoder will ask for them
-            hoist_decoder_map(l)
+        if hoist:
+            for l in range(nlev, 0 if hoist0_main else -1, -1):   # in the order the decoder will ask for them
+                hoist_map(self.dec_map[l], dec_cl, l)
 
         def table_early(split, Cm, early_feats, src_xyz):
             """second stream, beside the feature-transfer block that is about to run on the main stream: the part of a
@@ -2402,7 +2393,7 @@ class FusedCloudConditionNet:
         # (the first block's query conv reads x_t only: issued before the wait for the first neighbourhoods)
         q0 = None
         if QUERY_CONV_AHEAD and SPLIT_QUERY_CONV and QUERIES_IN_PLACE and USE_SPLIT_FIRST and _PAR["stream"] is not None:
-            q0 = self.enc_map[0].att.query_conv(feat0.reshape(B * N, -1), B, N)
+            q0 = _ready(self.enc_map[0].att.query_conv(feat0.reshape(B * N, -1), B, N))
         main.wait_event(ev_fm[0])
         mark("main:after_wait_first_ball_query")
         l_feat = [feat0]
@@ -2415,11 +2406,10 @@ class FusedCloudConditionNet:
                               q_ahead=q0 if i == 0 else None)
             mark("main:enc_map%d_done" % i)
             if i == 0 and hoist0_main and hoist and tables.get(id(self.dec_map[0])) is not None:
-                saved_par, _PAR["stream"] = _PAR["stream"], None
-                prepared[id(self.dec_map[0])] = (self.dec_map[0].prepare(
-                    l_uvw[0], dec_cl[0], l_xyz[0], bank, subset=False, neigh=fm_neigh[fm_key(0, self.dec_map[0])],
-                    V2=tables.get(id(self.dec_map[0]))), None)
-                _PAR["stream"] = saved_par
+                with _single_stream():
+                    prepared[id(self.dec_map[0])] = self.dec_map[0].prepare(
+                        l_uvw[0], dec_cl[0], l_xyz[0], bank, subset=False, neigh=fm_neigh[fm_key(0, self.dec_map[0])],
+                        V2=tables.get(id(self.dec_map[0])))
             sa_in = Cat(mapped, l_feat[i]) if USE_SPLIT_FIRST else torch.cat([mapped, l_feat[i]], dim=2)
             U_ahead = table_late(sa.split, pend, mapped)
             if i == 0 and SA0_TABLE_AHEAD and USE_SPLIT_FIRST and hoist0_main and _PAR["stream"] is not None:
