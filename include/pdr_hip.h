@@ -59,7 +59,7 @@ typedef void *pdr_stream_t; /* hipStream_t */
  *                before `stream`, pdr_gn_fold gained nvalid_a / tpb_main_a / nvalid_b / tpb_main_b, pdr_layer_in_t gained
  *                wrow0 / wmul / patch_values / patch_ld / patch_w before `reserved_`; round 6: pdr_layer_in_t.oadd_rows, probe_out is a 4-slot ring
  *                (int[16]), pdr_set_option replaces the environment knobs, pdr_point_chain / pdr_point_chain_plan /
- *                pdr_fused_layer_pair are new. */
+ *                pdr_fused_layer_pair are new; pdr_knn_points_ragged / pdr_chamfer_nn_ragged are new. */
 int pdr_version(void);
 /* last hip error string seen by this thread after a PDR_ELAUNCH ("" if none) */
 const char *pdr_last_error(void);
@@ -155,6 +155,17 @@ int pdr_three_interpolate_grad(const float *grad_out, const int *idx,
  * history) instead of index order and may keep another of several points tied at the K-th distance.) */
 int pdr_knn_points(const float *x, const float *y, int B, int n1, int n2, int K,
                    float *dists, int64_t *idx, float *nn, pdr_stream_t stream);
+/* pdr_knn_points with pytorch3d's per-cloud lengths: cloud b searches y[b, :lengths2[b]] for the queries
+ * x[b, :lengths1[b]]; n1 / n2 stay the padded sizes (row strides).  lengths1 / lengths2 are int64 arrays of B entries
+ * in DEVICE memory, read by the kernels only and clamped there to [0, n1] / [0, n2]: the host never reads them, so the
+ * call neither synchronises nor allocates and is capturable like the dense one (a replayed graph follows the lengths
+ * then in memory).  NULL = every cloud is full.  Rows at or beyond a cloud's length are never candidates, whatever
+ * they hold.  Every slot k >= lengths2[b] of a valid query and every slot of a padded query (p >= lengths1[b]) gets
+ * dist 0, idx -1, nn 0 -- the dense rule for K > n2.  Distance arithmetic, scan order, the tie rule, validation,
+ * return codes and the kernel choice (a function of n2 and K) are those of pdr_knn_points; with NULL or full lengths
+ * the output is bit-identical to it. */
+int pdr_knn_points_ragged(const float *x, const float *y, const int64_t *lengths1, const int64_t *lengths2,
+                          int B, int n1, int n2, int K, float *dists, int64_t *idx, float *nn, pdr_stream_t stream);
 
 /* Both nearest-neighbour searches of one Chamfer evaluation (chamfer_loss_new.py:149-150: knn_points(x, y, K=1)
  * and knn_points(y, x, K=1)) in ONE launch: dist_xy / idx_xy (B,n1) = squared distance and index of the nearest
@@ -162,6 +173,14 @@ int pdr_knn_points(const float *x, const float *y, int B, int n1, int n2, int K,
  * chamfer3D.cu:26-129).  Bit-identical to two pdr_knn_points(K = 1) calls. */
 int pdr_chamfer_nn(const float *x, const float *y, int B, int n1, int n2, float *dist_xy,
                    int64_t *idx_xy, float *dist_yx, int64_t *idx_yx, pdr_stream_t stream);
+/* pdr_chamfer_nn with per-cloud lengths (same rules as pdr_knn_points_ragged: device int64, clamped on the device,
+ * NULL = full), still ONE launch for both directions: lengths1 bounds x as queries of dist_xy and as candidates of
+ * dist_yx, lengths2 bounds y the other way round.  Padded queries, and valid queries whose opposite cloud is empty,
+ * get dist 0 and idx 0 (NOT -1: chamfer_distance gathers normals with these indices and masks the padded entries).
+ * With NULL or full lengths bit-identical to pdr_chamfer_nn. */
+int pdr_chamfer_nn_ragged(const float *x, const float *y, const int64_t *lengths1, const int64_t *lengths2,
+                          int B, int n1, int n2, float *dist_xy, int64_t *idx_xy, float *dist_yx, int64_t *idx_yx,
+                          pdr_stream_t stream);
 /* pdr_knn_points for group_knn (pointnet2_utils.py:487-514) inside the fused network: same search, int32 indices
  * and the normalised interpolation weights w = (1/(d2+1e-8)) / sum_k (1/(d2_k+1e-8)) of :500-503 (SQUARED
  * distances, k ascending) in the same pass.  Requires K <= min(n2, 16). */
@@ -173,7 +192,9 @@ int pdr_knn_group(const float *x, const float *y, int B, int n1, int n2, int K, 
  * K = 1 cross-check: chamfer3D.cu:155-195):
  *   grad_x[p] = sum_k 2 g[p,k] (x[p] - y[idx[p,k]]),  grad_y[j] = -sum_{idx[p,k] = j} (same term).
  * idx < 0 (padding) is skipped.  grad_x (B,n1,3) is overwritten; grad_y (B,n2,3) is zeroed on the
- * stream and accumulated with float atomics (summation order not fixed). */
+ * stream and accumulated with float atomics (summation order not fixed).
+ * This skip is also what makes pdr_knn_points_ragged differentiable without a kernel of its own: its padded queries
+ * and the slots beyond a cloud's length carry idx -1, so padded rows of either cloud receive exactly zero. */
 int pdr_knn_points_grad(const float *x, const float *y, const int64_t *idx,
                         const float *grad_dists, int B, int n1, int n2, int K,
                         float *grad_x, float *grad_y, pdr_stream_t stream);

@@ -22,18 +22,35 @@ constexpr int kTile = 1024;
 
 enum DistModel { kSum3 = 0, kAcc3 = 1 };
 
-template <int K, int MODEL, typename IdxT, bool KNN_PAD>
+// Per-cloud lengths (pytorch3d lengths1 / lengths2; pdr_knn_points_ragged, pdr_chamfer_nn_ragged): the RAGGED
+// instantiations of the three search kernels read cloud b's length here, on the device, clamped to [0, n]; n stays
+// the row stride.  Queries at or beyond their cloud's length search nothing and get the padding output, rows at or
+// beyond the searched cloud's length are never candidates.  NULL = every cloud is full.
+__device__ __forceinline__ int cloud_len(const int64_t* __restrict__ len, int b, int n) {
+  if (!len) return n;
+  const int64_t v = len[b];
+  return v < 0 ? 0 : (v > n ? n : static_cast<int>(v));
+}
+
+template <int K, int MODEL, typename IdxT, bool KNN_PAD, bool RAGGED = false>
 __global__ __launch_bounds__(256) void nn_search_kernel(const float* __restrict__ queries,
                                                         const float* __restrict__ cloud, int nq,
                                                         int nc, int Kout,
                                                         float* __restrict__ dists,
                                                         IdxT* __restrict__ idx,
                                                         float* __restrict__ nn,
-                                                        float* __restrict__ wgt = nullptr) {
+                                                        float* __restrict__ wgt = nullptr,
+                                                        const int64_t* __restrict__ len_q = nullptr,
+                                                        const int64_t* __restrict__ len_c = nullptr) {
+  static_assert(KNN_PAD || !RAGGED, "the ragged search pads with (0, -1)");
   __shared__ float4 tile[kTile];
   const int b = blockIdx.y;
   const int j = blockIdx.x * 256 + threadIdx.x;
   const bool active = j < nq;
+  // RAGGED: nce candidates, nqe searching queries; a workgroup of padded queries only scans nothing
+  const int nqe = RAGGED ? cloud_len(len_q, b, nq) : nq;
+  const int nce = !RAGGED ? nc : (static_cast<int>(blockIdx.x) * 256 < nqe ? cloud_len(len_c, b, nc) : 0);
+  const bool searching = RAGGED ? j < nqe : active;
   const float* q = queries + (static_cast<size_t>(b) * nq + (active ? j : 0)) * 3;
   const float* c = cloud + static_cast<size_t>(b) * nc * 3;
   const float qx = q[0], qy = q[1], qz = q[2];
@@ -46,15 +63,15 @@ __global__ __launch_bounds__(256) void nn_search_kernel(const float* __restrict_
     bi[t] = KNN_PAD ? -1 : 0;
   }
 
-  for (int k0 = 0; k0 < nc; k0 += kTile) {
-    const int kn = (nc - k0) < kTile ? (nc - k0) : kTile;
+  for (int k0 = 0; k0 < nce; k0 += kTile) {
+    const int kn = (nce - k0) < kTile ? (nce - k0) : kTile;
     __syncthreads();
     for (int t = threadIdx.x; t < kn; t += 256) {
       const float* s = c + static_cast<size_t>(k0 + t) * 3;
       tile[t] = make_float4(s[0], s[1], s[2], 0.0f);
     }
     __syncthreads();
-    if (active) {
+    if (searching) {
       for (int t = 0; t < kn; ++t) {
         const float4 pt = tile[t];
         const float dx = qx - pt.x, dy = qy - pt.y, dz = qz - pt.z;
@@ -122,11 +139,18 @@ __global__ __launch_bounds__(256) void nn_search_kernel(const float* __restrict_
 //      + one 64-bit compare per candidate; ranks < K are the answer in ascending order, equal distances by lower
 //      index, exactly the contract of the sorted-insertion kernel (bit-identical outputs, tested).
 // More than 64 candidates (massive exact ties) take an exact K-round minimum extraction instead.
-template <int NCH, typename IdxT>
+// RAGGED (cloud_len above): slots at or beyond the cloud's length hold +inf like the slots beyond nc, are never
+// candidates and never win the extraction.  A cloud shorter than 57 points leaves an 8-lane group without a point and
+// T = +inf: all its (< 64) points are candidates and the rank path orders them.  A cloud shorter than K has fewer
+// candidates than K and takes the extraction, whose exhausted key reads as index -1: such slots are written as
+// padding (0, -1, nn 0).
+template <int NCH, typename IdxT, bool RAGGED = false>
 __global__ __launch_bounds__(256) void knn_wave_kernel(const float* __restrict__ queries,
                                                        const float* __restrict__ cloud, int nq, int nc, int K,
                                                        int qpw, float* __restrict__ dists, IdxT* __restrict__ idx,
-                                                       float* __restrict__ nn, float* __restrict__ wgt) {
+                                                       float* __restrict__ nn, float* __restrict__ wgt,
+                                                       const int64_t* __restrict__ len_q = nullptr,
+                                                       const int64_t* __restrict__ len_c = nullptr) {
   __shared__ unsigned long long cand[4][64];
   __shared__ float outd[4][8];
   __shared__ int outi[4][8];
@@ -136,6 +160,8 @@ __global__ __launch_bounds__(256) void knn_wave_kernel(const float* __restrict__
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const float* c = cloud + static_cast<size_t>(b) * nc * 3;
   const float* q = queries + static_cast<size_t>(b) * nq * 3;
+  const int nqe = RAGGED ? cloud_len(len_q, b, nq) : nq;
+  const int nce = RAGGED ? cloud_len(len_c, b, nc) : nc;
   float px[NCH], py[NCH], pz[NCH];
   // (unconditional loads from a clamped slot, all in flight together; a load under `k < nc` is a branch with its
   // own wait: 16 dependent round trips before the first query)
@@ -149,7 +175,7 @@ __global__ __launch_bounds__(256) void knn_wave_kernel(const float* __restrict__
 #pragma unroll
   for (int ch = 0; ch < NCH; ++ch) {
     // out-of-range slots: +inf -> d = +inf, behind every real point
-    const bool ok = ch * 64 + lane < nc;
+    const bool ok = ch * 64 + lane < nce;
     px[ch] = ok ? px[ch] : __builtin_inff();
     py[ch] = ok ? py[ch] : __builtin_inff();
     pz[ch] = ok ? pz[ch] : __builtin_inff();
@@ -168,6 +194,15 @@ __global__ __launch_bounds__(256) void knn_wave_kernel(const float* __restrict__
     {
       const int jn = min(j + 1, nq - 1);
       nqx = q[jn * 3 + 0], nqy = q[jn * 3 + 1], nqz = q[jn * 3 + 2];
+    }
+    if (RAGGED && j >= nqe) {   // padded query (wave-uniform): nothing to search
+      if (lane < K) {
+        const size_t o = (static_cast<size_t>(b) * nq + j) * K + lane;
+        dists[o] = 0.0f;
+        idx[o] = static_cast<IdxT>(-1);
+        if (nn) nn[o * 3 + 0] = nn[o * 3 + 1] = nn[o * 3 + 2] = 0.0f;
+      }
+      continue;
     }
     float d[NCH];
     float m = __builtin_inff();
@@ -210,7 +245,7 @@ __global__ __launch_bounds__(256) void knn_wave_kernel(const float* __restrict__
 #pragma unroll
     for (int ch = 0; ch < NCH; ++ch) {
       const unsigned bits = __float_as_uint(d[ch]);
-      const bool hit = bits <= T;
+      const bool hit = bits <= T && (!RAGGED || ch * 64 + lane < nce);
       const unsigned long long mask = __ballot(hit);
       if (mask != 0ull) {
         const int pos = base + __builtin_amdgcn_mbcnt_hi(static_cast<unsigned>(mask >> 32),
@@ -221,8 +256,9 @@ __global__ __launch_bounds__(256) void knn_wave_kernel(const float* __restrict__
     }
     __builtin_amdgcn_wave_barrier();
     // base < K happens only when the distances are NaN (a non-finite query or point): no candidate passes
-    // `bits <= T`.  Those queries take the exact extraction below, which orders NaN keys by index and never leaves
-    // the output slots unwritten (the rank path then wrote nothing and stale LDS was stored).
+    // `bits <= T` -- or, RAGGED, when the cloud is shorter than K.  Those queries take the exact extraction below,
+    // which orders NaN keys by index and never leaves the output slots unwritten (the rank path then wrote
+    // nothing and stale LDS was stored).
     if (base >= K && base <= 64) {
       const unsigned long long key = lane < base ? cand[wave][lane] : ~0ull;
       const unsigned klo = static_cast<unsigned>(key), khi = static_cast<unsigned>(key >> 32);
@@ -245,7 +281,7 @@ __global__ __launch_bounds__(256) void knn_wave_kernel(const float* __restrict__
         for (int ch = 0; ch < NCH; ++ch) {
           // (slots beyond the cloud never win: with NaN distances their +inf would sort FIRST as unsigned bits)
           const unsigned long long key =
-              ch * 64 + lane < nc ? pdr::u64_from(__float_as_uint(d[ch]), static_cast<unsigned>(ch * 64 + lane))
+              ch * 64 + lane < nce ? pdr::u64_from(__float_as_uint(d[ch]), static_cast<unsigned>(ch * 64 + lane))
                                   : ~0ull;
           if ((r == 0 || key > last) && key < best) best = key;
         }
@@ -259,15 +295,18 @@ __global__ __launch_bounds__(256) void knn_wave_kernel(const float* __restrict__
     }
     __builtin_amdgcn_wave_barrier();
     if (lane < K) {
-      const float dk = outd[wave][lane];
-      const int ik = outi[wave][lane];
+      // RAGGED: an index at or beyond the length (the extraction's exhausted key reads as -1) is a padding slot
+      const bool empty = RAGGED && static_cast<unsigned>(outi[wave][lane]) >= static_cast<unsigned>(nce);
+      const float dk = empty ? 0.0f : outd[wave][lane];
+      const int ik = empty ? -1 : outi[wave][lane];
       const size_t o = (static_cast<size_t>(b) * nq + j) * K + lane;
       dists[o] = dk;
       idx[o] = static_cast<IdxT>(ik);
       if (nn) {
-        nn[o * 3 + 0] = c[ik * 3 + 0];
-        nn[o * 3 + 1] = c[ik * 3 + 1];
-        nn[o * 3 + 2] = c[ik * 3 + 2];
+        const int a = empty ? 0 : ik;
+        nn[o * 3 + 0] = empty ? 0.0f : c[a * 3 + 0];
+        nn[o * 3 + 1] = empty ? 0.0f : c[a * 3 + 1];
+        nn[o * 3 + 2] = empty ? 0.0f : c[a * 3 + 2];
       }
       if (wgt) {
         // group_knn's weights (pointnet2_utils.py:500-503), normalisation summed in ascending-k order as above
@@ -284,9 +323,9 @@ __global__ __launch_bounds__(256) void knn_wave_kernel(const float* __restrict__
 }
 
 // returns true when the wave-per-query kernel took the call
-template <typename IdxT>
+template <typename IdxT, bool RAGGED = false>
 bool launch_knn_wave(const float* x, const float* y, int B, int n1, int n2, int K, float* dists, IdxT* idx, float* nn,
-                     float* wgt, hipStream_t s) {
+                     float* wgt, hipStream_t s, const int64_t* len1 = nullptr, const int64_t* len2 = nullptr) {
   const bool on = pdr::option(pdr::OPT_KNN_WAVE) != 0;
   if (!on || K > 8 || n2 < 64 || n2 > 1024) return false;
   // queries per wave: amortise the register fill of the cloud while the launch keeps >= 1024 workgroups (measured at
@@ -294,8 +333,9 @@ bool launch_knn_wave(const float* x, const float* y, int B, int n1, int n2, int 
   int qpw = 16;
   while (qpw > 1 && static_cast<long long>(B) * ((n1 + 4 * qpw - 1) / (4 * qpw)) < 1024) qpw >>= 1;
   const dim3 grid((n1 + 4 * qpw - 1) / (4 * qpw), B);
-#define PDR_KW(NCH)                                                                                          \
-  hipLaunchKernelGGL((knn_wave_kernel<NCH, IdxT>), grid, dim3(256), 0, s, x, y, n1, n2, K, qpw, dists, idx, nn, wgt)
+#define PDR_KW(NCH)                                                                                                  \
+  hipLaunchKernelGGL((knn_wave_kernel<NCH, IdxT, RAGGED>), grid, dim3(256), 0, s, x, y, n1, n2, K, qpw, dists, idx, nn, \
+                     wgt, len1, len2)
   if (n2 <= 64) PDR_KW(1);
   else if (n2 <= 128) PDR_KW(2);
   else if (n2 <= 256) PDR_KW(4);
@@ -318,13 +358,17 @@ bool launch_knn_wave(const float* x, const float* y, int B, int n1, int n2, int 
 //     chunk of each query is rescanned in ascending order with strict `<`, which returns the first (lowest-index)
 //     point attaining the minimum = "first minimum wins" (chamfer3D.cu:26-129, pdr_hip.h knn contract).
 // ~4 issue slots per pair.  blockIdx.z selects the direction so both searches of a Chamfer evaluation are one launch.
+// RAGGED (cloud_len above): len_a / len_b bound xa / xb per cloud, as queries in one direction and as candidates in
+// the other; padded queries and queries of an empty cloud get (0, pad_idx): -1 for knn_points, 0 for Chamfer.
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
-template <int QP, typename IdxT>
+template <int QP, typename IdxT, bool RAGGED = false>
 __global__ __launch_bounds__(256) void nn1_kernel(const float* __restrict__ xa, const float* __restrict__ xb,
                                                   int na, int nb, float* __restrict__ da,
                                                   IdxT* __restrict__ ia, float* __restrict__ db,
-                                                  IdxT* __restrict__ ib) {
+                                                  IdxT* __restrict__ ib,
+                                                  const int64_t* __restrict__ len_a = nullptr,
+                                                  const int64_t* __restrict__ len_b = nullptr, int pad_idx = -1) {
   constexpr int CH = 8;
   constexpr int NQ = 2 * QP;                       // queries per thread
   __shared__ float4 tile[kTile];
@@ -339,6 +383,10 @@ __global__ __launch_bounds__(256) void nn1_kernel(const float* __restrict__ xa, 
   const float* c = cloud + static_cast<size_t>(b) * nc * 3;
   // thread t owns queries q0 + t + 256 i (coalesced loads / stores); out-of-range slots shadow the last query
   const int q0 = blockIdx.x * 256 * NQ + threadIdx.x;
+  const int nqe = RAGGED ? cloud_len(dir ? len_b : len_a, b, nq) : nq;
+  // (a workgroup of padded queries scans nothing)
+  const int nce =
+      !RAGGED ? nc : (static_cast<int>(blockIdx.x) * 256 * NQ < nqe ? cloud_len(dir ? len_a : len_b, b, nc) : 0);
   f32x2 qx[QP], qy[QP], qz[QP], best[QP];
   int bchunk[NQ];
 #pragma unroll
@@ -354,8 +402,8 @@ __global__ __launch_bounds__(256) void nn1_kernel(const float* __restrict__ xa, 
     }
     best[p] = f32x2{__builtin_inff(), __builtin_inff()};
   }
-  for (int k0 = 0; k0 < nc; k0 += kTile) {
-    const int kn = (nc - k0) < kTile ? (nc - k0) : kTile;
+  for (int k0 = 0; k0 < nce; k0 += kTile) {
+    const int kn = (nce - k0) < kTile ? (nce - k0) : kTile;
     const int kpad = (kn + CH - 1) / CH * CH;
     __syncthreads();
     for (int t = threadIdx.x; t < kpad; t += 256) {
@@ -405,7 +453,7 @@ __global__ __launch_bounds__(256) void nn1_kernel(const float* __restrict__ xa, 
       const int cs = bchunk[2 * p + h];
       for (int u = 0; u < CH; ++u) {
         const int k = cs + u;
-        if (k < nc) {
+        if (k < (RAGGED && j >= nqe ? 0 : nce)) {
           const float dx = x0 - c[k * 3 + 0], dy = y0 - c[k * 3 + 1], dz = z0 - c[k * 3 + 2];
           const float d = PDR_ACC3(dx, dy, dz);
           if (d < lb) {
@@ -416,7 +464,7 @@ __global__ __launch_bounds__(256) void nn1_kernel(const float* __restrict__ xa, 
       }
       const size_t o = static_cast<size_t>(b) * nq + j;
       dists[o] = li < 0 ? 0.0f : lb;                           // empty cloud: pytorch3d padding (0, -1)
-      idx[o] = static_cast<IdxT>(li);
+      idx[o] = static_cast<IdxT>(RAGGED && li < 0 ? pad_idx : li);
     }
   }
 }
@@ -425,12 +473,52 @@ __global__ __launch_bounds__(256) void nn1_kernel(const float* __restrict__ xa, 
 #define PDR_NN1_QP 2     // query PAIRS per thread of the K = 1 kernel (lab builds: -DPDR_NN1_QP=4)
 #endif
 
-template <int K>
-int launch_knn(const float* x, const float* y, int B, int n1, int n2, int Kout, float* dists,
-               int64_t* idx, float* nn, hipStream_t s) {
+template <int K, bool RAGGED>
+int launch_knn(const float* x, const float* y, const int64_t* len1, const int64_t* len2, int B, int n1, int n2,
+               int Kout, float* dists, int64_t* idx, float* nn, hipStream_t s) {
   dim3 grid((n1 + 255) / 256, B);
-  hipLaunchKernelGGL((nn_search_kernel<K, kAcc3, int64_t, true>), grid, dim3(256), 0, s, x, y, n1,
-                     n2, Kout, dists, idx, nn);
+  hipLaunchKernelGGL((nn_search_kernel<K, kAcc3, int64_t, true, RAGGED>), grid, dim3(256), 0, s, x, y, n1,
+                     n2, Kout, dists, idx, nn, static_cast<float*>(nullptr), len1, len2);
+  return pdr::check_launch();
+}
+
+// pdr_knn_points (RAGGED = false, no lengths) and pdr_knn_points_ragged: one validation, one dispatch on (n2, K)
+template <bool RAGGED>
+int knn_points(const float* x, const float* y, const int64_t* len1, const int64_t* len2, int B, int n1, int n2, int K,
+               float* dists, int64_t* idx, float* nn, pdr_stream_t stream) {
+  if (B < 0 || n1 < 0 || n2 < 0 || K <= 0) return PDR_EINVAL;
+  if (K > 32) return PDR_EUNSUPPORTED;
+  if (B == 0 || n1 == 0) return PDR_OK;
+  if (!x || !dists || !idx || (n2 > 0 && !y)) return PDR_EINVAL;
+  hipStream_t s = pdr::as_stream(stream);
+  if (K == 1 && !nn && n2 > 0) {
+    // dedicated packed-math kernel (one direction of pdr_chamfer_nn); bit-identical results
+    constexpr int QPB = 256 * 2 * PDR_NN1_QP;   // queries per workgroup
+    hipLaunchKernelGGL((nn1_kernel<PDR_NN1_QP, int64_t, RAGGED>), dim3((n1 + QPB - 1) / QPB, B, 1), dim3(256), 0, s, x,
+                       y, n1, n2, dists, idx, static_cast<float*>(nullptr), static_cast<int64_t*>(nullptr), len1, len2,
+                       -1);
+    return pdr::check_launch();
+  }
+  if (K == 1) return launch_knn<1, RAGGED>(x, y, len1, len2, B, n1, n2, K, dists, idx, nn, s);
+  if (K <= n2 && launch_knn_wave<int64_t, RAGGED>(x, y, B, n1, n2, K, dists, idx, nn, nullptr, s, len1, len2))
+    return pdr::check_launch();
+  if (K <= 4) return launch_knn<4, RAGGED>(x, y, len1, len2, B, n1, n2, K, dists, idx, nn, s);
+  if (K <= 8) return launch_knn<8, RAGGED>(x, y, len1, len2, B, n1, n2, K, dists, idx, nn, s);
+  if (K <= 16) return launch_knn<16, RAGGED>(x, y, len1, len2, B, n1, n2, K, dists, idx, nn, s);
+  return launch_knn<32, RAGGED>(x, y, len1, len2, B, n1, n2, K, dists, idx, nn, s);
+}
+
+// pdr_chamfer_nn and pdr_chamfer_nn_ragged: both directions in one launch
+template <bool RAGGED>
+int chamfer_nn(const float* x, const float* y, const int64_t* len1, const int64_t* len2, int B, int n1, int n2,
+               float* dist_xy, int64_t* idx_xy, float* dist_yx, int64_t* idx_yx, pdr_stream_t stream) {
+  if (B < 0 || n1 <= 0 || n2 <= 0) return PDR_EINVAL;
+  if (B == 0) return PDR_OK;
+  if (!x || !y || !dist_xy || !idx_xy || !dist_yx || !idx_yx) return PDR_EINVAL;
+  const int nmax = n1 > n2 ? n1 : n2;
+  constexpr int QPB = 256 * 2 * PDR_NN1_QP;
+  hipLaunchKernelGGL((nn1_kernel<PDR_NN1_QP, int64_t, RAGGED>), dim3((nmax + QPB - 1) / QPB, B, 2), dim3(256), 0,
+                     pdr::as_stream(stream), x, y, n1, n2, dist_xy, idx_xy, dist_yx, idx_yx, len1, len2, 0);
   return pdr::check_launch();
 }
 
@@ -450,24 +538,16 @@ extern "C" int pdr_three_nn(const float* unknown, const float* known, int B, int
 
 extern "C" int pdr_knn_points(const float* x, const float* y, int B, int n1, int n2, int K,
                               float* dists, int64_t* idx, float* nn, pdr_stream_t stream) {
-  if (B < 0 || n1 < 0 || n2 < 0 || K <= 0) return PDR_EINVAL;
-  if (K > 32) return PDR_EUNSUPPORTED;
-  if (B == 0 || n1 == 0) return PDR_OK;
-  if (!x || !dists || !idx || (n2 > 0 && !y)) return PDR_EINVAL;
-  hipStream_t s = pdr::as_stream(stream);
-  if (K == 1 && !nn && n2 > 0) {
-    // dedicated packed-math kernel (one direction of pdr_chamfer_nn); bit-identical results
-    constexpr int QPB = 256 * 2 * PDR_NN1_QP;   // queries per workgroup
-    hipLaunchKernelGGL((nn1_kernel<PDR_NN1_QP, int64_t>), dim3((n1 + QPB - 1) / QPB, B, 1), dim3(256), 0, s, x, y, n1,
-                       n2, dists, idx, static_cast<float*>(nullptr), static_cast<int64_t*>(nullptr));
-    return pdr::check_launch();
-  }
-  if (K == 1) return launch_knn<1>(x, y, B, n1, n2, K, dists, idx, nn, s);
-  if (K <= n2 && launch_knn_wave<int64_t>(x, y, B, n1, n2, K, dists, idx, nn, nullptr, s)) return pdr::check_launch();
-  if (K <= 4) return launch_knn<4>(x, y, B, n1, n2, K, dists, idx, nn, s);
-  if (K <= 8) return launch_knn<8>(x, y, B, n1, n2, K, dists, idx, nn, s);
-  if (K <= 16) return launch_knn<16>(x, y, B, n1, n2, K, dists, idx, nn, s);
-  return launch_knn<32>(x, y, B, n1, n2, K, dists, idx, nn, s);
+  return knn_points<false>(x, y, nullptr, nullptr, B, n1, n2, K, dists, idx, nn, stream);
+}
+
+// pdr_knn_points with pytorch3d's lengths1 / lengths2 (device int64, read by the kernels only; NULL = full).  Without
+// any lengths this IS the dense call.
+extern "C" int pdr_knn_points_ragged(const float* x, const float* y, const int64_t* lengths1, const int64_t* lengths2,
+                                     int B, int n1, int n2, int K, float* dists, int64_t* idx, float* nn,
+                                     pdr_stream_t stream) {
+  if (!lengths1 && !lengths2) return knn_points<false>(x, y, nullptr, nullptr, B, n1, n2, K, dists, idx, nn, stream);
+  return knn_points<true>(x, y, lengths1, lengths2, B, n1, n2, K, dists, idx, nn, stream);
 }
 
 // Both nearest-neighbour searches of a Chamfer evaluation (chamfer_loss_new.py:149-150, 166-167) in ONE launch:
@@ -475,14 +555,17 @@ extern "C" int pdr_knn_points(const float* x, const float* y, int B, int n1, int
 // Identical to two pdr_knn_points(K = 1) calls, bit for bit.
 extern "C" int pdr_chamfer_nn(const float* x, const float* y, int B, int n1, int n2, float* dist_xy,
                               int64_t* idx_xy, float* dist_yx, int64_t* idx_yx, pdr_stream_t stream) {
-  if (B < 0 || n1 <= 0 || n2 <= 0) return PDR_EINVAL;
-  if (B == 0) return PDR_OK;
-  if (!x || !y || !dist_xy || !idx_xy || !dist_yx || !idx_yx) return PDR_EINVAL;
-  const int nmax = n1 > n2 ? n1 : n2;
-  constexpr int QPB = 256 * 2 * PDR_NN1_QP;
-  hipLaunchKernelGGL((nn1_kernel<PDR_NN1_QP, int64_t>), dim3((nmax + QPB - 1) / QPB, B, 2), dim3(256), 0,
-                     pdr::as_stream(stream), x, y, n1, n2, dist_xy, idx_xy, dist_yx, idx_yx);
-  return pdr::check_launch();
+  return chamfer_nn<false>(x, y, nullptr, nullptr, B, n1, n2, dist_xy, idx_xy, dist_yx, idx_yx, stream);
+}
+
+// pdr_chamfer_nn over x[b, :lengths1[b]] and y[b, :lengths2[b]], still one launch; padded queries and queries of an
+// empty opposite cloud get (0, 0), what chamfer_distance's masking expects.
+extern "C" int pdr_chamfer_nn_ragged(const float* x, const float* y, const int64_t* lengths1, const int64_t* lengths2,
+                                     int B, int n1, int n2, float* dist_xy, int64_t* idx_xy, float* dist_yx,
+                                     int64_t* idx_yx, pdr_stream_t stream) {
+  if (!lengths1 && !lengths2)
+    return chamfer_nn<false>(x, y, nullptr, nullptr, B, n1, n2, dist_xy, idx_xy, dist_yx, idx_yx, stream);
+  return chamfer_nn<true>(x, y, lengths1, lengths2, B, n1, n2, dist_xy, idx_xy, dist_yx, idx_yx, stream);
 }
 
 // knn_points for the fused network's feature propagation (group_knn, pointnet2_utils.py:487-514): the same search

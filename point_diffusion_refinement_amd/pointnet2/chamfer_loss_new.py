@@ -5,9 +5,10 @@ The two nearest-neighbour searches (pytorch3d knn_points K=1 in the reference,
 :149-150) run on libpdr_hip.so: ONE launch for both directions (pdr_chamfer_nn) on the
 hot path = dense clouds of equal length per batch without gradient (what
 completion_eval.py feeds); two differentiable knn_points calls when a gradient is
-needed (train.py:518).  Ragged `x_lengths` / `y_lengths` take a slow per-sample path
-over the same kernels (reference :121-128, 152-155 semantics: padded points are not
-candidates and contribute 0); pytorch3d `Pointclouds` objects are rejected.
+needed (train.py:518).  Ragged `x_lengths` / `y_lengths` take the same two routes: the
+kernels read the per-cloud lengths on the device (pdr_chamfer_nn_ragged, one launch;
+length-aware knn_points with a gradient), reference :121-128, 152-155 semantics: padded
+points are not candidates and contribute 0.  pytorch3d `Pointclouds` objects are rejected.
 All distances are SQUARED; cd_p takes the square root per point before the mean;
 the F-score threshold is applied to squared distances.
 """
@@ -58,9 +59,30 @@ def _nearest_both(x, y):
     return _ext.chamfer_nn(x.contiguous(), y.contiguous())
 
 
-def _nearest_ragged(a, la, b, lb):
-    """Slow path for heterogeneous lengths: sample n searches a[n, :la[n]] in b[n, :lb[n]]; padded queries get
-    distance 0 / index 0 (what the reference's masking leaves, :152-155)."""
+def _nearest_lengths(a, la, b, lb):
+    """Differentiable search of a[n, :la[n]] in b[n, :lb[n]]: padded queries and queries of an empty cloud come back
+    as (0, -1); index 0 instead keeps the normals gather in range (those entries are masked, or have no neighbour)."""
+    d, i, _ = _ext.knn_points(a.contiguous(), b.contiguous(), 1, lengths1=la, lengths2=lb)
+    return d[..., 0], i[..., 0].clamp(min=0)
+
+
+def _nearest_both_ragged(x, x_lengths, y, y_lengths):
+    """(cham_x, idx_x, cham_y, idx_y) of padded clouds, sample n being x[n, :x_lengths[n]] and y[n, :y_lengths[n]]:
+    padded queries get distance 0 / index 0 (what the reference's masking leaves, :152-155).  The kernels read the
+    lengths on the device: one launch without autograd, two differentiable searches otherwise."""
+    if not x.is_cuda:
+        return _nearest_per_sample(x, x_lengths, y, y_lengths) + _nearest_per_sample(y, y_lengths, x, x_lengths)
+    lx = x_lengths.to(device=x.device, dtype=torch.int64).contiguous()
+    ly = y_lengths.to(device=y.device, dtype=torch.int64).contiguous()
+    if torch.is_grad_enabled() and (x.requires_grad or y.requires_grad):
+        return _nearest_lengths(x, lx, y, ly) + _nearest_lengths(y, ly, x, lx)
+    return _ext.chamfer_nn(x.contiguous(), y.contiguous(), lx, ly)
+
+
+def _nearest_per_sample(a, la, b, lb):
+    """Tensors that are not on a GPU: `_ext` has no implementation for them, so this is reached only with a backend
+    substituted for it that knows the dense signatures alone (tests/oracle_backend.py); one dense search per sample
+    over the slices, same results."""
     d = a.new_zeros(a.shape[:2])
     i = torch.zeros(a.shape[:2], dtype=torch.int64, device=a.device)
     for n in range(a.shape[0]):
@@ -99,8 +121,7 @@ def chamfer_distance(x, y, x_lengths=None, y_lengths=None, x_normals=None, y_nor
     if ragged:
         if bool((x_lengths > P1).any()) or bool((y_lengths > P2).any()):
             raise ValueError("lengths exceed the padded size")
-        cham_x, idx_x = _nearest_ragged(x, x_lengths, y, y_lengths)
-        cham_y, idx_y = _nearest_ragged(y, y_lengths, x, x_lengths)
+        cham_x, idx_x, cham_y, idx_y = _nearest_both_ragged(x, x_lengths, y, y_lengths)
         x_mask = torch.arange(P1, device=x.device)[None] >= x_lengths[:, None]
         y_mask = torch.arange(P2, device=y.device)[None] >= y_lengths[:, None]
     else:

@@ -179,28 +179,52 @@ def three_interpolate_grad(grad_out, idx, weight, m):
     return out
 
 
-def _knn_forward(p1, p2, K, return_nn):
+def _req_lengths(t, name, cloud):
+    """pytorch3d per-cloud lengths: (B,) int64 on the clouds' device, or None (every cloud full).  The values stay on
+    the device: the kernels read and clamp them, nothing here does."""
+    if t is None:
+        return
+    _req(t, name, torch.int64)
+    if t.dim() != 1 or t.shape[0] != cloud.shape[0]:
+        raise RuntimeError("%s must have shape (B,) = (%d,), got %s" % (name, cloud.shape[0], tuple(t.shape)))
+    _same_device(cloud, t)
+
+
+def _ptr(t):
+    return t.data_ptr() if t is not None else None
+
+
+def _knn_forward(p1, p2, K, return_nn, lengths1=None, lengths2=None):
     B, n1, _ = p1.shape
     n2 = p2.shape[1]
     dists = torch.empty((B, n1, K), dtype=torch.float32, device=p1.device)
     idx = torch.empty((B, n1, K), dtype=torch.int64, device=p1.device)
     nn = torch.empty((B, n1, K, 3), dtype=torch.float32, device=p1.device) if return_nn else None
     with torch.cuda.device(p1.device):
-        _lib.check(_lib.load().pdr_knn_points(p1.data_ptr(), p2.data_ptr(), B, n1, n2, int(K), dists.data_ptr(),
-                                              idx.data_ptr(), nn.data_ptr() if return_nn else None, _stream()),
-                   "knn_points")
+        if lengths1 is None and lengths2 is None:
+            rc = _lib.load().pdr_knn_points(p1.data_ptr(), p2.data_ptr(), B, n1, n2, int(K), dists.data_ptr(),
+                                            idx.data_ptr(), _ptr(nn), _stream())
+        else:
+            rc = _lib.load().pdr_knn_points_ragged(p1.data_ptr(), p2.data_ptr(), _ptr(lengths1), _ptr(lengths2), B,
+                                                   n1, n2, int(K), dists.data_ptr(), idx.data_ptr(), _ptr(nn),
+                                                   _stream())
+        _lib.check(rc, "knn_points")
     return dists, idx, nn
 
 
-def chamfer_nn(x, y):
+def chamfer_nn(x, y, x_lengths=None, y_lengths=None):
     """Both K = 1 searches of a Chamfer evaluation in one launch:
     (B,n1,3), (B,n2,3) -> (dist_xy (B,n1), idx_xy (B,n1) i64, dist_yx (B,n2), idx_yx (B,n2) i64); not differentiable
-    (chamfer_distance uses knn_points when a gradient is needed)."""
+    (chamfer_distance uses knn_points when a gradient is needed).  With `x_lengths` / `y_lengths` ((B,) int64 on the
+    clouds' device) cloud b is x[b, :x_lengths[b]] / y[b, :y_lengths[b]]; padded queries and queries of an empty
+    opposite cloud get distance 0 and index 0."""
     _req(x, "x", torch.float32)
     _req(y, "y", torch.float32)
     _same_device(x, y)
     if x.shape[2] != 3 or y.shape[2] != 3 or x.shape[0] != y.shape[0]:
         raise RuntimeError("chamfer_nn: (B,n,3) clouds with equal batch size")
+    _req_lengths(x_lengths, "x_lengths", x)
+    _req_lengths(y_lengths, "y_lengths", y)
     B, n1, _ = x.shape
     n2 = y.shape[1]
     dx = torch.empty((B, n1), dtype=torch.float32, device=x.device)
@@ -208,8 +232,14 @@ def chamfer_nn(x, y):
     ix = torch.empty((B, n1), dtype=torch.int64, device=x.device)
     iy = torch.empty((B, n2), dtype=torch.int64, device=x.device)
     with torch.cuda.device(x.device):
-        _lib.check(_lib.load().pdr_chamfer_nn(x.data_ptr(), y.data_ptr(), B, n1, n2, dx.data_ptr(), ix.data_ptr(),
-                                              dy.data_ptr(), iy.data_ptr(), _stream()), "chamfer_nn")
+        if x_lengths is None and y_lengths is None:
+            rc = _lib.load().pdr_chamfer_nn(x.data_ptr(), y.data_ptr(), B, n1, n2, dx.data_ptr(), ix.data_ptr(),
+                                            dy.data_ptr(), iy.data_ptr(), _stream())
+        else:
+            rc = _lib.load().pdr_chamfer_nn_ragged(x.data_ptr(), y.data_ptr(), _ptr(x_lengths), _ptr(y_lengths), B,
+                                                   n1, n2, dx.data_ptr(), ix.data_ptr(), dy.data_ptr(),
+                                                   iy.data_ptr(), _stream())
+        _lib.check(rc, "chamfer_nn")
     return dx, ix, dy, iy
 
 
@@ -242,11 +272,12 @@ def knn_group(x, y, K):
 
 
 class _KnnDists(torch.autograd.Function):
-    """Differentiable squared distances of knn_points (pytorch3d `_knn_points` backward, norm 2)."""
+    """Differentiable squared distances of knn_points (pytorch3d `_knn_points` backward, norm 2).  With lengths the
+    padded queries and slots carry idx -1, which pdr_knn_points_grad skips: padded rows get a zero gradient."""
 
     @staticmethod
-    def forward(ctx, p1, p2, K):
-        dists, idx, _ = _knn_forward(p1, p2, K, False)
+    def forward(ctx, p1, p2, K, lengths1=None, lengths2=None):
+        dists, idx, _ = _knn_forward(p1, p2, K, False, lengths1, lengths2)
         ctx.save_for_backward(p1, p2, idx)
         ctx.mark_non_differentiable(idx)
         return dists, idx
@@ -263,24 +294,28 @@ class _KnnDists(torch.autograd.Function):
             _lib.check(_lib.load().pdr_knn_points_grad(p1.data_ptr(), p2.data_ptr(), idx.data_ptr(), g.data_ptr(), B,
                                                        n1, n2, K, g1.data_ptr(), g2.data_ptr(), _stream()),
                        "knn_points_grad")
-        return g1, g2, None
+        return g1, g2, None, None, None
 
 
-def knn_points(p1, p2, K, return_nn=False):
-    """pytorch3d.ops.knn.knn_points on dense equal-length clouds:
+def knn_points(p1, p2, K, return_nn=False, lengths1=None, lengths2=None):
+    """pytorch3d.ops.knn.knn_points on padded clouds:
     (B,n1,3), (B,n2,3) -> (dists (B,n1,K) f32 squared ascending, idx (B,n1,K) i64, nn (B,n1,K,3) | None).
+    `lengths1` / `lengths2` ((B,) int64 on the clouds' device, None = full): cloud b searches p2[b, :lengths2[b]] for
+    the queries p1[b, :lengths1[b]]; slots beyond lengths2[b] and every slot of a padded query are (0, -1, nn 0).
     With grad enabled and an input that requires it, `dists` (and `nn`, as a gather of p2) are differentiable."""
     _req(p1, "p1", torch.float32)
     _req(p2, "p2", torch.float32)
     _same_device(p1, p2)
     if p1.shape[2] != 3 or p2.shape[2] != 3:
         raise RuntimeError("knn_points: only D=3 is built")
+    _req_lengths(lengths1, "lengths1", p1)
+    _req_lengths(lengths2, "lengths2", p2)
     if torch.is_grad_enabled() and (p1.requires_grad or p2.requires_grad):
-        dists, idx = _KnnDists.apply(p1, p2, int(K))
+        dists, idx = _KnnDists.apply(p1, p2, int(K), lengths1, lengths2)
         nn = None
         if return_nn:
             B, n1, _ = p1.shape
             safe = idx.clamp(min=0).reshape(B, n1 * int(K), 1).expand(-1, -1, 3)
             nn = p2.gather(1, safe).reshape(B, n1, int(K), 3) * (idx >= 0).unsqueeze(-1)
         return dists, idx, nn
-    return _knn_forward(p1, p2, K, return_nn)
+    return _knn_forward(p1, p2, K, return_nn, lengths1, lengths2)
