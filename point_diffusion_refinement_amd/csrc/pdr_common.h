@@ -29,6 +29,8 @@ inline int check_launch() {
 
 inline hipStream_t as_stream(pdr_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 
+inline unsigned blocks_for(long total) { return static_cast<unsigned>((total + 255) / 256); }   // 256-thread workgroups
+
 // Process-wide kernel-selection options (pdr_set_option / pdr_get_option of include/pdr_hip.h; the table with names,
 // defaults and ranges is in abi.hip).  Rounds 1-5 read ten of them from the environment inside the library; since ABI
 // 0.2.0 the library never looks at the environment -- the caller sets them.

@@ -3,7 +3,7 @@
 //
 // Reference composition: Mlp_plus_t_emb (pointnet2_modules.py:69-174) as PointnetKnnFPModule applies it to the
 // interpolated features of a level (mlp2, :829-839), the query conv + first score conv of AttentionModule
-// (attention.py:70-82).  Layer by layer (fused_layer.hip) such a chain is conv launch -> GroupNorm fold launch -> conv
+// (attention.py:70-82).  Layer by layer (fused_layer.hip, gn_stats.hip, act_ops.hip) such a chain is conv launch -> GroupNorm fold launch -> conv
 // launch -> fold launch -> activation launch: five dependent launches of 5-30 us for a few microseconds of MFMA work at
 // the 16- / 64- / 256-point levels (profiles/r5_timeline.json: the chip holds one small kernel for 1.3 ms of a step).
 //
@@ -27,7 +27,7 @@
 // weight-row stride 144 floats make every operand read of the 16 x 4 / 4 x 16 fragments conflict-free.
 // Exact fp32 (same MFMA family as the layer kernels); results equal the layer-by-layer chain up to fp32 summation order
 // (the GroupNorm sums are taken in double from per-lane fp32 sums of at most 16 rows).
-#include "pdr_common.h"
+#include "gn_fold.h"
 
 #include <mutex>
 
@@ -358,14 +358,9 @@ __global__ __launch_bounds__(512, 1) void point_chain_kernel(pdr_point_chain_t P
             g1 += sm.csum[g0 + j][0];
             g2 += sm.csum[g0 + j][1];
           }
-          // the arithmetic of gn_fold_kernel (fused_layer.hip)
-          const double cnt = static_cast<double>(n) * cpg;
-          const double mean = g1 / cnt;
-          double var = g2 / cnt - mean * mean;
-          if (var < 0.0) var = 0.0;
-          const float rstd = static_cast<float>(1.0 / sqrt(var + static_cast<double>(L.eps)));
-          sc = rstd * L.gamma[col];
-          sh = __builtin_fmaf(-sc, static_cast<float>(mean), L.beta[col]);
+          const pdr::GnAffine a = pdr::gn_scale_shift(g1, g2, static_cast<double>(n) * cpg, L.eps, L.gamma, L.beta, col);
+          sc = a.scale;
+          sh = a.shift;
         }
         sm.ss[tid][0] = sc;
         sm.ss[tid][1] = sh;

@@ -1604,6 +1604,76 @@ def test_gn_fold_skips_the_invalid_tile_range(cuda):
         assert bool(torch.isfinite(outs[1][0]).all())
 
 
+# every route from tile moments to a folded GroupNorm: (tiles per batch element of the parts, widths of the parts,
+# Cn, G, options, entry points).  B = 3; C = 79 > Cn leaves pass-through channels behind the normalised range.
+_FOLD_ROUTES = {
+    "small_u4": ((2,), (79,), 64, 32, {}, "fold"),
+    "small_u16": ((130,), (79,), 64, 32, {}, "fold"),            # > 128 tiles: 16 rows in flight per thread
+    "two_parts": ((5, 3), (48, 31), 64, 32, {}, "fold"),         # the normalised range spans both sources
+    "wide_cpg48": ((5,), (111,), 96, 2, {}, "fold"),             # 48 channels per group: no 32-channel window
+    "wide_option": ((5,), (79,), 64, 32, {"gn_fold_small": 0}, "fold"),
+    "reduce_finalize": ((5,), (79,), 64, 32, {}, "reduce"),
+}
+
+
+@pytest.mark.parametrize("route", sorted(_FOLD_ROUTES))
+def test_gn_fold_routes_agree_with_a_float64_fold(cuda, route):
+    """Every route from per-tile moments to (scale, shift) -- pdr_gn_fold in its small form with 4 and with 16 rows in
+    flight, with two sources, in its wide form (chosen by the group width and by option gn_fold_small = 0), and
+    pdr_gn_reduce + pdr_gn_finalize -- against a float64 fold of the same synthetic `partial` rows.
+
+    Tolerance, from the arithmetic: the routes differ from the reference only in the order of their double sums over
+    float inputs (about 2^-53 per term), which can flip one float rounding and no more.  scale = float(rstd) * gamma is
+    one rounding of rstd and one float product: at most 2 float ulp.  shift = fma(-scale, float(mean), beta) adds the
+    rounding of mean and of the fma: |d shift| <= 2^-22 (|scale mean| + |beta|).  Channels >= Cn are exactly (1, 0)."""
+    from tests.layer_cases import options
+    tpbs, widths, Cn, G, opts, entry = _FOLD_ROUTES[route]
+    lib, dev = _lib.load(), cuda
+    st = torch.cuda.current_stream().cuda_stream
+    B, C, eps = 3, sum(widths), 1e-5
+    g = torch.Generator(device=dev).manual_seed(sum(map(ord, route)))
+    parts, mults = [], (1.0, 4.0)
+    for tpb, Cp in zip(tpbs, widths):   # (sum x, sum x^2) of 128 values per tile and channel
+        parts.append(torch.stack([torch.randn(B * tpb, Cp, device=dev, generator=g) * 8.0,
+                                  (torch.rand(B * tpb, Cp, device=dev, generator=g) + 0.5) * 128.0], -1).contiguous())
+    n = float(tpbs[0] * 128)
+    gamma, beta = torch.rand(C, device=dev, generator=g) + 0.5, torch.randn(C, device=dev, generator=g)
+    scale, shift = torch.empty(B, C, device=dev), torch.empty(B, C, device=dev)
+    with options(opts):
+        if entry == "fold":
+            second = (None, 0, 0, 0, 1.0)
+            if len(parts) > 1:
+                second = (parts[1].data_ptr(), widths[1], tpbs[1], widths[1], mults[1])
+            _lib.check(lib.pdr_gn_fold(parts[0].data_ptr(), widths[0], tpbs[0], widths[0], mults[0], *second, B, Cn, G, n,
+                                       eps, gamma.data_ptr(), beta.data_ptr(), scale.data_ptr(), shift.data_ptr(), None, 0,
+                                       None, 0, st), "gn_fold")
+        else:
+            stats = torch.empty(B, C, 2, device=dev, dtype=torch.float64)
+            _lib.check(lib.pdr_gn_reduce(parts[0].data_ptr(), C, B, tpbs[0], C, mults[0], stats.data_ptr(), C, 0, st),
+                       "gn_reduce")
+            _lib.check(lib.pdr_gn_finalize(stats.data_ptr(), B, C, Cn, G, n, eps, gamma.data_ptr(), beta.data_ptr(),
+                                           scale.data_ptr(), shift.data_ptr(), st), "gn_finalize")
+    torch.cuda.synchronize()
+    got_sc, got_sh = scale.cpu().numpy(), shift.cpu().numpy()
+
+    mom = np.concatenate([p.cpu().numpy().astype(np.float64).reshape(B, tpb, Cp, 2).sum(1) * m
+                          for p, tpb, Cp, m in zip(parts, tpbs, widths, mults)], 1)          # (B, C, 2)
+    cpg = Cn // G
+    grp = mom[:, :Cn].reshape(B, G, cpg, 2).sum(2) / (n * cpg)                              # (B, G, 2)
+    mean = np.repeat(grp[..., 0], cpg, 1)
+    var = np.repeat(np.maximum(grp[..., 1] - grp[..., 0] ** 2, 0.0), cpg, 1)
+    ga, be = gamma.cpu().numpy().astype(np.float64)[:Cn], beta.cpu().numpy().astype(np.float64)[:Cn]
+    want_sc = ga / np.sqrt(var + float(np.float32(eps)))
+    want_sh = be - want_sc * mean
+    ulp = np.spacing(np.abs(want_sc).astype(np.float32)).astype(np.float64)
+    err_sc = np.abs(got_sc[:, :Cn] - want_sc) / ulp
+    err_sh = np.abs(got_sh[:, :Cn] - want_sh) / (2.0 ** -22 * (np.abs(want_sc * mean) + np.abs(be)))
+    print("%s: scale error %.3f ulp (bound 2), shift error %.3f of its bound" % (route, err_sc.max(), err_sh.max()))
+    assert err_sc.max() <= 2.0 and err_sh.max() <= 1.0
+    assert np.all(got_sc[:, Cn:] == 1.0) and np.all(got_sh[:, Cn:] == 0.0)
+    assert C > Cn and var.min() > 0.1   # pass-through channels exist; no group sits on the variance clamp
+
+
 @pytest.mark.parametrize("D,K", [(32, 32), (64, 32), (128, 8)])
 def test_pooled_launch_patches_the_skipped_queries(cuda, D, K):
     """pdr_layer_in_t.patch_values / patch_w on a pooled launch over a tile subset with a row map = the same launch
