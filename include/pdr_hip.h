@@ -59,7 +59,8 @@ typedef void *pdr_stream_t; /* hipStream_t */
  *                before `stream`, pdr_gn_fold gained nvalid_a / tpb_main_a / nvalid_b / tpb_main_b, pdr_layer_in_t gained
  *                wrow0 / wmul / patch_values / patch_ld / patch_w before `reserved_`; round 6: pdr_layer_in_t.oadd_rows, probe_out is a 4-slot ring
  *                (int[16]), pdr_set_option replaces the environment knobs, pdr_point_chain / pdr_point_chain_plan /
- *                pdr_fused_layer_pair are new; pdr_knn_points_ragged / pdr_chamfer_nn_ragged are new. */
+ *                pdr_fused_layer_pair are new; pdr_knn_points_ragged / pdr_chamfer_nn_ragged are new; pdr_approxmatch_ragged /
+ *                pdr_emd_cost_ragged / pdr_matchcost_ragged / pdr_matchcost_grad_ragged are new. */
 int pdr_version(void);
 /* last hip error string seen by this thread after a PDR_ELAUNCH ("" if none) */
 const char *pdr_last_error(void);
@@ -222,6 +223,34 @@ int pdr_matchcost_grad(const float *grad_cost, const float *xyz1,
                        int m, float *grad1, float *grad2, pdr_stream_t stream);
 int pdr_emd_cost(const float *xyz1, const float *xyz2, int B, int n, int m,
                  float *cost, float *temp, pdr_stream_t stream);
+/* The four EMD calls with per-cloud lengths (the rules of pdr_knn_points_ragged: lengths1 / lengths2 are int64 arrays
+ * of B entries in DEVICE memory, read by the kernels only and clamped there to [0, n] / [0, m]; the host never reads
+ * them, so the calls neither synchronise nor allocate, stay capturable, and a replayed graph follows the lengths then
+ * in memory; NULL = every cloud is full).  Cloud b is the pair xyz1[b, :n_b], xyz2[b, :m_b] with n_b = lengths1[b],
+ * m_b = lengths2[b]; n / m stay the padded sizes: the row strides of xyz1, xyz2, match, the gradients and the
+ * workspace, and the sizes pdr_emd_workspace_bytes / pdr_matchcost_workspace_bytes are asked with.  The reference has
+ * no such call; the contract is that cloud b gets exactly what the dense call gives on the two slices:
+ *   - the factors multiL / multiR (emd_kernel.cu:31-38) are per cloud, from (n_b, m_b) with the same integer division,
+ *     computed on the device;
+ *   - rows at or beyond a cloud's length are never candidates and never reach an output, whatever they hold (NaN
+ *     included); the loops over the opposite cloud run to m_b / n_b, sequentially from index 0 in tiles of 1024, so
+ *     the valid region is computed by the dense kernels' operation sequence (bit-identical to the dense call on the
+ *     slices, cost included: the reductions over k do not depend on the padded n);
+ *   - every output is fully written: match[b, l, k] = 0 for l >= m_b or k >= n_b (pdr_matchcost_ragged and
+ *     pdr_matchcost_grad_ragged never READ those entries of a given match), gradient rows of padded points are
+ *     exactly 0, cost[b] sums valid rows only;
+ *   - a pair with n_b == 0 or m_b == 0 is empty: nothing is divided, cost 0, match rows 0, gradients 0.
+ * Validation and return codes are the dense calls'; the launches are the dense calls' (same kernels' grids over the
+ * padded sizes, same count); with NULL or full lengths the output is bit-identical to the dense call. */
+int pdr_approxmatch_ragged(const float *xyz1, const float *xyz2, const int64_t *lengths1, const int64_t *lengths2,
+                           int B, int n, int m, float *match, float *temp, pdr_stream_t stream);
+int pdr_matchcost_ragged(const float *xyz1, const float *xyz2, const int64_t *lengths1, const int64_t *lengths2,
+                         const float *match, int B, int n, int m, float *cost, float *temp, pdr_stream_t stream);
+int pdr_matchcost_grad_ragged(const float *grad_cost, const float *xyz1, const float *xyz2, const int64_t *lengths1,
+                              const int64_t *lengths2, const float *match, int B, int n, int m, float *grad1,
+                              float *grad2, pdr_stream_t stream);
+int pdr_emd_cost_ragged(const float *xyz1, const float *xyz2, const int64_t *lengths1, const int64_t *lengths2,
+                        int B, int n, int m, float *cost, float *temp, pdr_stream_t stream);
 
 /* ==== fused channel-LAST layer kernels ========================================
  * These have no single pybind counterpart: each replaces a COMPOSITION of torch ops

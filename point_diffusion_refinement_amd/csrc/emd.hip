@@ -21,6 +21,14 @@
 //    read the same address (broadcast).  Per-thread accumulation order over the
 //    opposite cloud is sequential, as in the reference, so the only numeric
 //    difference to the oracle is __expf (v_exp_f32) vs expf.
+//
+// Per-cloud lengths (pdr_*_ragged): every kernel is ONE body with a RAGGED switch; the dense entry points instantiate
+// it off and pass no lengths, so they run the code they always ran.  Switched on, cloud b is the pair
+// xyz1[b, :ne], xyz2[b, :me] (pair_len: read on the device, clamped, an empty side empties the pair); n and m stay the
+// row strides and the grid sizes.  A thread whose own row is padding keeps walking the tile loops' barriers and does
+// not write; a workgroup whose rows are ALL padding gets a loop bound of 0 (uniform over the workgroup).  The loops over
+// the opposite cloud run to me / ne from index 0 in the same tiles, so the valid region is computed by the dense
+// operation sequence on the slices, and nothing beyond a length is ever loaded -- points, workspace or match.
 #include "pdr_common.h"
 
 namespace {
@@ -57,33 +65,66 @@ __device__ inline Ws ws_of(float* temp, int b, int n, int m) {
   return w;
 }
 
+// Valid sizes of pair b: (n, m) without RAGGED; else lengths1[b] / lengths2[b] clamped to [0, n] / [0, m] (NULL = full),
+// and (0, 0) when either is 0 -- an empty pair has no candidates, no rows and nothing to divide.
+struct PairLen {
+  int n, m;
+};
+template <bool RAGGED>
+__device__ __forceinline__ PairLen pair_len(const int64_t* __restrict__ len1,
+                                            const int64_t* __restrict__ len2, int b, int n, int m) {
+  PairLen p{n, m};
+  if (RAGGED) {
+    if (len1) { const int64_t v = len1[b]; p.n = v < 0 ? 0 : (v > n ? n : static_cast<int>(v)); }
+    if (len2) { const int64_t v = len2[b]; p.m = v < 0 ? 0 : (v > m ? m : static_cast<int>(v)); }
+    if (p.n == 0 || p.m == 0) p.n = p.m = 0;
+  }
+  return p;
+}
+
+// RAGGED: multiL / multiR are the pair's own (emd_kernel.cu:31-38 on (ne, me), same integer division)
+template <bool RAGGED>
 __global__ __launch_bounds__(256) void emd_init_kernel(float* temp, int n, int m, float multiL,
-                                                       float multiR) {
+                                                       float multiR,
+                                                       const int64_t* __restrict__ len1 = nullptr,
+                                                       const int64_t* __restrict__ len2 = nullptr) {
   const Ws w = ws_of(temp, blockIdx.y, n, m);
+  const PairLen len = pair_len<RAGGED>(len1, len2, blockIdx.y, n, m);
+  const int ne = len.n, me = len.m;
+  if (RAGGED && ne > 0) {   // (ne > 0 implies me > 0)
+    if (ne >= me) { multiL = 1.0f; multiR = static_cast<float>(ne / me); }
+    else          { multiL = static_cast<float>(me / ne); multiR = 1.0f; }
+  }
   const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i < n) {
+  if (i < ne) {
     w.remainL[i] = multiL;
     w.costpart[i] = 0.0f;
   }
-  if (i < m) w.remainR[i] = multiR;
+  if (i < me) w.remainR[i] = multiR;
 }
 
 // pass 1 (emd_kernel.cu:55-88): ratioL[k] = remainL[k] / (1e-9 + sum_l exp(level d) remainR[l])
+template <bool RAGGED>
 __global__ __launch_bounds__(256) void emd_pass1_kernel(const float* __restrict__ xyz1,
                                                         const float* __restrict__ xyz2,
-                                                        float* temp, int n, int m, int li) {
+                                                        float* temp, int n, int m, int li,
+                                                        const int64_t* __restrict__ len1 = nullptr,
+                                                        const int64_t* __restrict__ len2 = nullptr) {
   __shared__ float4 tile[kTile];
   const int b = blockIdx.y;
   const Ws w = ws_of(temp, b, n, m);
+  const PairLen len = pair_len<RAGGED>(len1, len2, b, n, m);
+  const int ne = len.n;
+  const int me = RAGGED && static_cast<int>(blockIdx.x) * 256 >= ne ? 0 : len.m;
   const float level = level_value(li);
   const int k = blockIdx.x * 256 + threadIdx.x;
   const float* p1 = xyz1 + static_cast<size_t>(b) * n * 3;
   const float* p2 = xyz2 + static_cast<size_t>(b) * m * 3;
   float x1 = 0, y1 = 0, z1 = 0;
-  if (k < n) { x1 = p1[k * 3]; y1 = p1[k * 3 + 1]; z1 = p1[k * 3 + 2]; }
+  if (k < ne) { x1 = p1[k * 3]; y1 = p1[k * 3 + 1]; z1 = p1[k * 3 + 2]; }
   float suml = 1e-9f;
-  for (int l0 = 0; l0 < m; l0 += kTile) {
-    const int lend = (m - l0) < kTile ? (m - l0) : kTile;
+  for (int l0 = 0; l0 < me; l0 += kTile) {
+    const int lend = (me - l0) < kTile ? (me - l0) : kTile;
     __syncthreads();
     for (int l = threadIdx.x; l < lend; l += 256)
       tile[l] = make_float4(p2[(l0 + l) * 3], p2[(l0 + l) * 3 + 1], p2[(l0 + l) * 3 + 2],
@@ -96,26 +137,32 @@ __global__ __launch_bounds__(256) void emd_pass1_kernel(const float* __restrict_
       suml = __builtin_fmaf(__expf(d), t.w, suml);   // single-use product: contracted (model N1)
     }
   }
-  if (k < n) w.ratioL[static_cast<size_t>(li) * n + k] = w.remainL[k] / suml;
+  if (k < ne) w.ratioL[static_cast<size_t>(li) * n + k] = w.remainL[k] / suml;
 }
 
 // pass 2 (emd_kernel.cu:90-122)
+template <bool RAGGED>
 __global__ __launch_bounds__(256) void emd_pass2_kernel(const float* __restrict__ xyz1,
                                                         const float* __restrict__ xyz2,
-                                                        float* temp, int n, int m, int li) {
+                                                        float* temp, int n, int m, int li,
+                                                        const int64_t* __restrict__ len1 = nullptr,
+                                                        const int64_t* __restrict__ len2 = nullptr) {
   __shared__ float4 tile[kTile];
   const int b = blockIdx.y;
   const Ws w = ws_of(temp, b, n, m);
+  const PairLen len = pair_len<RAGGED>(len1, len2, b, n, m);
+  const int me = len.m;
+  const int ne = RAGGED && static_cast<int>(blockIdx.x) * 256 >= me ? 0 : len.n;
   const float level = level_value(li);
   const float* ratioL = w.ratioL + static_cast<size_t>(li) * n;
   const int l = blockIdx.x * 256 + threadIdx.x;
   const float* p1 = xyz1 + static_cast<size_t>(b) * n * 3;
   const float* p2 = xyz2 + static_cast<size_t>(b) * m * 3;
   float x2 = 0, y2 = 0, z2 = 0;
-  if (l < m) { x2 = p2[l * 3]; y2 = p2[l * 3 + 1]; z2 = p2[l * 3 + 2]; }
+  if (l < me) { x2 = p2[l * 3]; y2 = p2[l * 3 + 1]; z2 = p2[l * 3 + 2]; }
   float sumr = 0;
-  for (int k0 = 0; k0 < n; k0 += kTile) {
-    const int kend = (n - k0) < kTile ? (n - k0) : kTile;
+  for (int k0 = 0; k0 < ne; k0 += kTile) {
+    const int kend = (ne - k0) < kTile ? (ne - k0) : kTile;
     __syncthreads();
     for (int k = threadIdx.x; k < kend; k += 256)
       tile[k] = make_float4(p1[(k0 + k) * 3], p1[(k0 + k) * 3 + 1], p1[(k0 + k) * 3 + 2],
@@ -127,7 +174,7 @@ __global__ __launch_bounds__(256) void emd_pass2_kernel(const float* __restrict_
       sumr = __builtin_fmaf(__expf(level * PDR_SUM3(dx, dy, dz)), t.w, sumr);   // model N1
     }
   }
-  if (l < m) {
+  if (l < me) {
     const float rr = w.remainR[l];
     sumr *= rr;
     const float consumption = fminf(rr / (sumr + 1e-9f), 1.0f);
@@ -138,25 +185,31 @@ __global__ __launch_bounds__(256) void emd_pass2_kernel(const float* __restrict_
 
 // pass 3 (emd_kernel.cu:124-157) without the match RMW; accumulates
 // costpart[k] += sum_l d2 * w  (what matchcost :226-231 would add for this level)
+template <bool RAGGED>
 __global__ __launch_bounds__(256) void emd_pass3_kernel(const float* __restrict__ xyz1,
                                                         const float* __restrict__ xyz2,
-                                                        float* temp, int n, int m, int li) {
+                                                        float* temp, int n, int m, int li,
+                                                        const int64_t* __restrict__ len1 = nullptr,
+                                                        const int64_t* __restrict__ len2 = nullptr) {
   __shared__ float4 tile[kTile];
   const int b = blockIdx.y;
   const Ws w = ws_of(temp, b, n, m);
+  const PairLen len = pair_len<RAGGED>(len1, len2, b, n, m);
+  const int ne = len.n;
+  const int me = RAGGED && static_cast<int>(blockIdx.x) * 256 >= ne ? 0 : len.m;
   const float level = level_value(li);
   const float* ratioR = w.ratioR + static_cast<size_t>(li) * m;
   const int k = blockIdx.x * 256 + threadIdx.x;
   const float* p1 = xyz1 + static_cast<size_t>(b) * n * 3;
   const float* p2 = xyz2 + static_cast<size_t>(b) * m * 3;
   float x1 = 0, y1 = 0, z1 = 0, rl = 0;
-  if (k < n) {
+  if (k < ne) {
     x1 = p1[k * 3]; y1 = p1[k * 3 + 1]; z1 = p1[k * 3 + 2];
     rl = w.ratioL[static_cast<size_t>(li) * n + k];
   }
   float suml = 0, cost = 0;
-  for (int l0 = 0; l0 < m; l0 += kTile) {
-    const int lend = (m - l0) < kTile ? (m - l0) : kTile;
+  for (int l0 = 0; l0 < me; l0 += kTile) {
+    const int lend = (me - l0) < kTile ? (me - l0) : kTile;
     __syncthreads();
     for (int l = threadIdx.x; l < lend; l += 256)
       tile[l] = make_float4(p2[(l0 + l) * 3], p2[(l0 + l) * 3 + 1], p2[(l0 + l) * 3 + 2],
@@ -171,7 +224,7 @@ __global__ __launch_bounds__(256) void emd_pass3_kernel(const float* __restrict_
       cost = __builtin_fmaf(d2, wgt, cost);
     }
   }
-  if (k < n) {
+  if (k < ne) {
     w.remainL[k] = fmaxf(0.0f, w.remainL[k] - suml);
     w.costpart[k] += cost;
   }
@@ -179,36 +232,47 @@ __global__ __launch_bounds__(256) void emd_pass3_kernel(const float* __restrict_
 
 // match[b,l,k] = sum_level exp(level d2) * ratioL[level][k] * ratioR[level][l]
 // thread <-> k (coalesced rows of match), block handles 16 rows l.
+// RAGGED: the grid still covers the padded (m, n) matrix; entries with l >= me or k >= ne are written as 0.
+template <bool RAGGED>
 __global__ __launch_bounds__(256) void emd_match_kernel(const float* __restrict__ xyz1,
                                                         const float* __restrict__ xyz2,
                                                         float* temp, int n, int m,
-                                                        float* __restrict__ match) {
+                                                        float* __restrict__ match,
+                                                        const int64_t* __restrict__ len1 = nullptr,
+                                                        const int64_t* __restrict__ len2 = nullptr) {
   constexpr int ROWS = 16;
   __shared__ float4 rows[ROWS];
   __shared__ float rr[ROWS][kLevels];
   const int b = blockIdx.z;
   const Ws w = ws_of(temp, b, n, m);
+  const PairLen len = pair_len<RAGGED>(len1, len2, b, n, m);
+  const int ne = len.n, me = len.m;
   const int k = blockIdx.x * 256 + threadIdx.x;
   const int l0 = blockIdx.y * ROWS;
   const float* p1 = xyz1 + static_cast<size_t>(b) * n * 3;
   const float* p2 = xyz2 + static_cast<size_t>(b) * m * 3;
   if (threadIdx.x < ROWS) {
     const int l = l0 + threadIdx.x;
-    rows[threadIdx.x] = l < m ? make_float4(p2[l * 3], p2[l * 3 + 1], p2[l * 3 + 2], 0.0f)
-                              : make_float4(0, 0, 0, 0);
+    rows[threadIdx.x] = l < me ? make_float4(p2[l * 3], p2[l * 3 + 1], p2[l * 3 + 2], 0.0f)
+                               : make_float4(0, 0, 0, 0);
   }
   if (threadIdx.x < ROWS * kLevels) {
     const int r = threadIdx.x / kLevels, li = threadIdx.x % kLevels;
-    rr[r][li] = (l0 + r) < m ? w.ratioR[static_cast<size_t>(li) * m + l0 + r] : 0.0f;
+    rr[r][li] = (l0 + r) < me ? w.ratioR[static_cast<size_t>(li) * m + l0 + r] : 0.0f;
   }
   __syncthreads();
   if (k >= n) return;
+  float* mt = match + static_cast<size_t>(b) * n * m;
+  if (RAGGED) {   // past the only barrier: rows of the padding, and this thread's whole column when it is padding
+    for (int r = k < ne ? (me > l0 ? me - l0 : 0) : 0; r < ROWS && l0 + r < m; ++r)
+      mt[static_cast<size_t>(l0 + r) * n + k] = 0.0f;
+    if (k >= ne) return;
+  }
   const float x1 = p1[k * 3], y1 = p1[k * 3 + 1], z1 = p1[k * 3 + 2];
   float rl[kLevels];
 #pragma unroll
   for (int li = 0; li < kLevels; ++li) rl[li] = w.ratioL[static_cast<size_t>(li) * n + k];
-  float* mt = match + static_cast<size_t>(b) * n * m;
-  for (int r = 0; r < ROWS && l0 + r < m; ++r) {
+  for (int r = 0; r < ROWS && l0 + r < me; ++r) {
     const float4 t = rows[r];
     const float dx = t.x - x1, dy = t.y - y1, dz = t.z - z1;
     const float d2 = PDR_SUM3(dx, dy, dz);
@@ -221,13 +285,18 @@ __global__ __launch_bounds__(256) void emd_match_kernel(const float* __restrict_
 }
 
 // cost[b] = sum_k costpart[k]  (deterministic tree)
+// RAGGED: over the ne valid rows; thread t adds rows t, t + 256, ... whatever the padded n is
+template <bool RAGGED>
 __global__ __launch_bounds__(256) void emd_cost_reduce_kernel(float* temp, int n, int m,
-                                                              float* __restrict__ cost) {
+                                                              float* __restrict__ cost,
+                                                              const int64_t* __restrict__ len1 = nullptr,
+                                                              const int64_t* __restrict__ len2 = nullptr) {
   __shared__ float part[4];
   const int b = blockIdx.x;
   const Ws w = ws_of(temp, b, n, m);
+  const int ne = pair_len<RAGGED>(len1, len2, b, n, m).n;
   float s = 0;
-  for (int k = threadIdx.x; k < n; k += 256) s += w.costpart[k];
+  for (int k = threadIdx.x; k < ne; k += 256) s += w.costpart[k];
   s = pdr::wave_sum_f32(s);
   if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
   __syncthreads();
@@ -235,27 +304,34 @@ __global__ __launch_bounds__(256) void emd_cost_reduce_kernel(float* temp, int n
 }
 
 // matchcost with a given match (emd_kernel.cu:204-246): block per (b, 256-wide k slab)
+// RAGGED: a slab of padding writes the partial +0, which sum_partials_kernel adds without changing a bit
+template <bool RAGGED>
 __global__ __launch_bounds__(256) void matchcost_kernel(const float* __restrict__ xyz1,
                                                         const float* __restrict__ xyz2,
                                                         const float* __restrict__ match, int n,
-                                                        int m, float* __restrict__ partial) {
+                                                        int m, float* __restrict__ partial,
+                                                        const int64_t* __restrict__ len1 = nullptr,
+                                                        const int64_t* __restrict__ len2 = nullptr) {
   __shared__ float4 tile[kTile];
   __shared__ float part[4];
   const int b = blockIdx.y;
+  const PairLen len = pair_len<RAGGED>(len1, len2, b, n, m);
+  const int ne = len.n;
+  const int me = RAGGED && static_cast<int>(blockIdx.x) * 256 >= ne ? 0 : len.m;
   const int k = blockIdx.x * 256 + threadIdx.x;
   const float* p1 = xyz1 + static_cast<size_t>(b) * n * 3;
   const float* p2 = xyz2 + static_cast<size_t>(b) * m * 3;
   const float* mt = match + static_cast<size_t>(b) * n * m;
   float x1 = 0, y1 = 0, z1 = 0;
-  if (k < n) { x1 = p1[k * 3]; y1 = p1[k * 3 + 1]; z1 = p1[k * 3 + 2]; }
+  if (k < ne) { x1 = p1[k * 3]; y1 = p1[k * 3 + 1]; z1 = p1[k * 3 + 2]; }
   float subsum = 0;
-  for (int l0 = 0; l0 < m; l0 += kTile) {
-    const int lend = (m - l0) < kTile ? (m - l0) : kTile;
+  for (int l0 = 0; l0 < me; l0 += kTile) {
+    const int lend = (me - l0) < kTile ? (me - l0) : kTile;
     __syncthreads();
     for (int l = threadIdx.x; l < lend; l += 256)
       tile[l] = make_float4(p2[(l0 + l) * 3], p2[(l0 + l) * 3 + 1], p2[(l0 + l) * 3 + 2], 0.0f);
     __syncthreads();
-    if (k < n) {
+    if (k < ne) {
       for (int l = 0; l < lend; ++l) {
         const float4 t = tile[l];
         const float dx = t.x - x1, dy = t.y - y1, dz = t.z - z1;
@@ -282,19 +358,29 @@ __global__ void sum_partials_kernel(const float* __restrict__ partial, int nblk,
 }
 
 // matchcostgrad1 (emd_kernel.cu:337-359): thread per xyz1 point, loop over xyz2
+// RAGGED: rows of the padding get exactly 0 (no barrier in this kernel: they leave at once)
+template <bool RAGGED>
 __global__ __launch_bounds__(256) void matchcost_grad1_kernel(
     const float* __restrict__ grad_cost, const float* __restrict__ xyz1,
     const float* __restrict__ xyz2, const float* __restrict__ match, int n, int m,
-    float* __restrict__ grad1) {
+    float* __restrict__ grad1, const int64_t* __restrict__ len1 = nullptr,
+    const int64_t* __restrict__ len2 = nullptr) {
   const int b = blockIdx.y;
   const int l = blockIdx.x * 256 + threadIdx.x;
   if (l >= n) return;
+  const PairLen len = pair_len<RAGGED>(len1, len2, b, n, m);
+  const int me = len.m;
+  if (RAGGED && l >= len.n) {
+    float* z = grad1 + (static_cast<size_t>(b) * n + l) * 3;
+    z[0] = 0.0f; z[1] = 0.0f; z[2] = 0.0f;
+    return;
+  }
   const float* p1 = xyz1 + static_cast<size_t>(b) * n * 3;
   const float* p2 = xyz2 + static_cast<size_t>(b) * m * 3;
   const float* mt = match + static_cast<size_t>(b) * n * m;
   const float x1 = p1[l * 3], y1 = p1[l * 3 + 1], z1 = p1[l * 3 + 2];
   float dx = 0, dy = 0, dz = 0;
-  for (int k = 0; k < m; ++k) {
+  for (int k = 0; k < me; ++k) {
     const float d = mt[static_cast<size_t>(k) * n + l] * 2;
     dx += (x1 - p2[k * 3 + 0]) * d;
     dy += (y1 - p2[k * 3 + 1]) * d;
@@ -306,20 +392,28 @@ __global__ __launch_bounds__(256) void matchcost_grad1_kernel(
 }
 
 // matchcostgrad2 (emd_kernel.cu:290-331): wave per xyz2 point, lanes stride over xyz1
+template <bool RAGGED>
 __global__ __launch_bounds__(256) void matchcost_grad2_kernel(
     const float* __restrict__ grad_cost, const float* __restrict__ xyz1,
     const float* __restrict__ xyz2, const float* __restrict__ match, int n, int m,
-    float* __restrict__ grad2) {
+    float* __restrict__ grad2, const int64_t* __restrict__ len1 = nullptr,
+    const int64_t* __restrict__ len2 = nullptr) {
   const int b = blockIdx.y;
   const int k = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (k >= m) return;
   const int lane = threadIdx.x & 63;
+  const PairLen len = pair_len<RAGGED>(len1, len2, b, n, m);
+  const int ne = len.n;
+  if (RAGGED && k >= len.m) {   // (k is the wave's: the whole wave leaves)
+    if (lane < 3) grad2[(static_cast<size_t>(b) * m + k) * 3 + lane] = 0.0f;
+    return;
+  }
   const float* p1 = xyz1 + static_cast<size_t>(b) * n * 3;
   const float* p2 = xyz2 + static_cast<size_t>(b) * m * 3;
   const float* mt = match + (static_cast<size_t>(b) * m + k) * n;
   const float x2 = p2[k * 3], y2 = p2[k * 3 + 1], z2 = p2[k * 3 + 2];
   float sx = 0, sy = 0, sz = 0;
-  for (int j = lane; j < n; j += 64) {
+  for (int j = lane; j < ne; j += 64) {
     const float d = mt[j] * 2;
     sx += (x2 - p1[j * 3 + 0]) * d;
     sy += (y2 - p1[j * 3 + 1]) * d;
@@ -335,20 +429,80 @@ __global__ __launch_bounds__(256) void matchcost_grad2_kernel(
   }
 }
 
-int run_levels(const float* xyz1, const float* xyz2, int B, int n, int m, float* temp,
-               hipStream_t s) {
-  float multiL, multiR;  // emd_kernel.cu:31-38, integer division
+// init + 10 levels of three passes: 31 launches over the padded sizes, with or without lengths
+template <bool RAGGED>
+int run_levels(const float* xyz1, const float* xyz2, const int64_t* len1, const int64_t* len2, int B,
+               int n, int m, float* temp, hipStream_t s) {
+  float multiL, multiR;  // emd_kernel.cu:31-38, integer division (RAGGED: redone per pair on the device)
   if (n >= m) { multiL = 1.0f; multiR = static_cast<float>(n / m); }
   else        { multiL = static_cast<float>(m / n); multiR = 1.0f; }
   const int nm = n > m ? n : m;
-  hipLaunchKernelGGL(emd_init_kernel, dim3((nm + 255) / 256, B), dim3(256), 0, s, temp, n, m,
-                     multiL, multiR);
+  hipLaunchKernelGGL(emd_init_kernel<RAGGED>, dim3((nm + 255) / 256, B), dim3(256), 0, s, temp, n, m,
+                     multiL, multiR, len1, len2);
   const dim3 gn((n + 255) / 256, B), gm((m + 255) / 256, B);
   for (int li = 0; li < kLevels; ++li) {
-    hipLaunchKernelGGL(emd_pass1_kernel, gn, dim3(256), 0, s, xyz1, xyz2, temp, n, m, li);
-    hipLaunchKernelGGL(emd_pass2_kernel, gm, dim3(256), 0, s, xyz1, xyz2, temp, n, m, li);
-    hipLaunchKernelGGL(emd_pass3_kernel, gn, dim3(256), 0, s, xyz1, xyz2, temp, n, m, li);
+    hipLaunchKernelGGL(emd_pass1_kernel<RAGGED>, gn, dim3(256), 0, s, xyz1, xyz2, temp, n, m, li, len1, len2);
+    hipLaunchKernelGGL(emd_pass2_kernel<RAGGED>, gm, dim3(256), 0, s, xyz1, xyz2, temp, n, m, li, len1, len2);
+    hipLaunchKernelGGL(emd_pass3_kernel<RAGGED>, gn, dim3(256), 0, s, xyz1, xyz2, temp, n, m, li, len1, len2);
   }
+  return pdr::check_launch();
+}
+
+// The four entry points, dense (RAGGED = false, no lengths) and with lengths: one validation, one launch sequence.
+template <bool RAGGED>
+int approxmatch(const float* xyz1, const float* xyz2, const int64_t* len1, const int64_t* len2, int B,
+                int n, int m, float* match, float* temp, pdr_stream_t stream) {
+  if (B < 0 || n <= 0 || m <= 0) return PDR_EINVAL;
+  if (B == 0) return PDR_OK;
+  if (!xyz1 || !xyz2 || !match || !temp) return PDR_EINVAL;
+  hipStream_t s = pdr::as_stream(stream);
+  int rc = run_levels<RAGGED>(xyz1, xyz2, len1, len2, B, n, m, temp, s);
+  if (rc != PDR_OK) return rc;
+  hipLaunchKernelGGL(emd_match_kernel<RAGGED>, dim3((n + 255) / 256, (m + 15) / 16, B), dim3(256), 0, s,
+                     xyz1, xyz2, temp, n, m, match, len1, len2);
+  return pdr::check_launch();
+}
+
+template <bool RAGGED>
+int emd_cost(const float* xyz1, const float* xyz2, const int64_t* len1, const int64_t* len2, int B, int n,
+             int m, float* cost, float* temp, pdr_stream_t stream) {
+  if (B < 0 || n <= 0 || m <= 0) return PDR_EINVAL;
+  if (B == 0) return PDR_OK;
+  if (!xyz1 || !xyz2 || !cost || !temp) return PDR_EINVAL;
+  hipStream_t s = pdr::as_stream(stream);
+  int rc = run_levels<RAGGED>(xyz1, xyz2, len1, len2, B, n, m, temp, s);
+  if (rc != PDR_OK) return rc;
+  hipLaunchKernelGGL(emd_cost_reduce_kernel<RAGGED>, dim3(B), dim3(256), 0, s, temp, n, m, cost, len1, len2);
+  return pdr::check_launch();
+}
+
+template <bool RAGGED>
+int matchcost(const float* xyz1, const float* xyz2, const int64_t* len1, const int64_t* len2,
+              const float* match, int B, int n, int m, float* cost, float* temp, pdr_stream_t stream) {
+  if (B < 0 || n <= 0 || m <= 0) return PDR_EINVAL;
+  if (B == 0) return PDR_OK;
+  if (!xyz1 || !xyz2 || !match || !cost || !temp) return PDR_EINVAL;
+  hipStream_t s = pdr::as_stream(stream);
+  // slab partials (B, ceil(n/256)) in `temp`, then a fixed-order sum: deterministic
+  const int nblk = (n + 255) / 256;
+  hipLaunchKernelGGL(matchcost_kernel<RAGGED>, dim3(nblk, B), dim3(256), 0, s, xyz1, xyz2, match, n, m,
+                     temp, len1, len2);
+  hipLaunchKernelGGL(sum_partials_kernel, dim3(B), dim3(64), 0, s, temp, nblk, cost);
+  return pdr::check_launch();
+}
+
+template <bool RAGGED>
+int matchcost_grad(const float* grad_cost, const float* xyz1, const float* xyz2, const int64_t* len1,
+                   const int64_t* len2, const float* match, int B, int n, int m, float* grad1,
+                   float* grad2, pdr_stream_t stream) {
+  if (B < 0 || n <= 0 || m <= 0) return PDR_EINVAL;
+  if (B == 0) return PDR_OK;
+  if (!grad_cost || !xyz1 || !xyz2 || !match || !grad1 || !grad2) return PDR_EINVAL;
+  hipStream_t s = pdr::as_stream(stream);
+  hipLaunchKernelGGL(matchcost_grad1_kernel<RAGGED>, dim3((n + 255) / 256, B), dim3(256), 0, s,
+                     grad_cost, xyz1, xyz2, match, n, m, grad1, len1, len2);
+  hipLaunchKernelGGL(matchcost_grad2_kernel<RAGGED>, dim3((m + 3) / 4, B), dim3(256), 0, s, grad_cost,
+                     xyz1, xyz2, match, n, m, grad2, len1, len2);
   return pdr::check_launch();
 }
 
@@ -359,60 +513,66 @@ extern "C" size_t pdr_emd_workspace_bytes(int B, int n, int m) {
   return sizeof(float) * static_cast<size_t>(B) * ws_floats(n, m);
 }
 
-extern "C" int pdr_approxmatch(const float* xyz1, const float* xyz2, int B, int n, int m,
-                               float* match, float* temp, pdr_stream_t stream) {
-  if (B < 0 || n <= 0 || m <= 0) return PDR_EINVAL;
-  if (B == 0) return PDR_OK;
-  if (!xyz1 || !xyz2 || !match || !temp) return PDR_EINVAL;
-  hipStream_t s = pdr::as_stream(stream);
-  int rc = run_levels(xyz1, xyz2, B, n, m, temp, s);
-  if (rc != PDR_OK) return rc;
-  hipLaunchKernelGGL(emd_match_kernel, dim3((n + 255) / 256, (m + 15) / 16, B), dim3(256), 0, s,
-                     xyz1, xyz2, temp, n, m, match);
-  return pdr::check_launch();
-}
-
-extern "C" int pdr_emd_cost(const float* xyz1, const float* xyz2, int B, int n, int m,
-                            float* cost, float* temp, pdr_stream_t stream) {
-  if (B < 0 || n <= 0 || m <= 0) return PDR_EINVAL;
-  if (B == 0) return PDR_OK;
-  if (!xyz1 || !xyz2 || !cost || !temp) return PDR_EINVAL;
-  hipStream_t s = pdr::as_stream(stream);
-  int rc = run_levels(xyz1, xyz2, B, n, m, temp, s);
-  if (rc != PDR_OK) return rc;
-  hipLaunchKernelGGL(emd_cost_reduce_kernel, dim3(B), dim3(256), 0, s, temp, n, m, cost);
-  return pdr::check_launch();
-}
-
 extern "C" size_t pdr_matchcost_workspace_bytes(int B, int n, int m) {
   if (B <= 0 || n <= 0 || m <= 0) return 0;
   return sizeof(float) * static_cast<size_t>(B) * ((n + 255) / 256);
 }
 
+extern "C" int pdr_approxmatch(const float* xyz1, const float* xyz2, int B, int n, int m,
+                               float* match, float* temp, pdr_stream_t stream) {
+  return approxmatch<false>(xyz1, xyz2, nullptr, nullptr, B, n, m, match, temp, stream);
+}
+
+extern "C" int pdr_emd_cost(const float* xyz1, const float* xyz2, int B, int n, int m,
+                            float* cost, float* temp, pdr_stream_t stream) {
+  return emd_cost<false>(xyz1, xyz2, nullptr, nullptr, B, n, m, cost, temp, stream);
+}
+
 extern "C" int pdr_matchcost(const float* xyz1, const float* xyz2, const float* match, int B,
                              int n, int m, float* cost, float* temp, pdr_stream_t stream) {
-  if (B < 0 || n <= 0 || m <= 0) return PDR_EINVAL;
-  if (B == 0) return PDR_OK;
-  if (!xyz1 || !xyz2 || !match || !cost || !temp) return PDR_EINVAL;
-  hipStream_t s = pdr::as_stream(stream);
-  // slab partials (B, ceil(n/256)) in `temp`, then a fixed-order sum: deterministic
-  const int nblk = (n + 255) / 256;
-  hipLaunchKernelGGL(matchcost_kernel, dim3(nblk, B), dim3(256), 0, s, xyz1, xyz2, match, n, m,
-                     temp);
-  hipLaunchKernelGGL(sum_partials_kernel, dim3(B), dim3(64), 0, s, temp, nblk, cost);
-  return pdr::check_launch();
+  return matchcost<false>(xyz1, xyz2, nullptr, nullptr, match, B, n, m, cost, temp, stream);
 }
 
 extern "C" int pdr_matchcost_grad(const float* grad_cost, const float* xyz1, const float* xyz2,
                                   const float* match, int B, int n, int m, float* grad1,
                                   float* grad2, pdr_stream_t stream) {
-  if (B < 0 || n <= 0 || m <= 0) return PDR_EINVAL;
-  if (B == 0) return PDR_OK;
-  if (!grad_cost || !xyz1 || !xyz2 || !match || !grad1 || !grad2) return PDR_EINVAL;
-  hipStream_t s = pdr::as_stream(stream);
-  hipLaunchKernelGGL(matchcost_grad1_kernel, dim3((n + 255) / 256, B), dim3(256), 0, s, grad_cost,
-                     xyz1, xyz2, match, n, m, grad1);
-  hipLaunchKernelGGL(matchcost_grad2_kernel, dim3((m + 3) / 4, B), dim3(256), 0, s, grad_cost,
-                     xyz1, xyz2, match, n, m, grad2);
-  return pdr::check_launch();
+  return matchcost_grad<false>(grad_cost, xyz1, xyz2, nullptr, nullptr, match, B, n, m, grad1, grad2,
+                               stream);
+}
+
+// The same calls with per-cloud lengths (device int64, read by the kernels only; NULL = full; include/pdr_hip.h).
+// Without any lengths each IS the dense call.
+extern "C" int pdr_approxmatch_ragged(const float* xyz1, const float* xyz2, const int64_t* lengths1,
+                                      const int64_t* lengths2, int B, int n, int m, float* match,
+                                      float* temp, pdr_stream_t stream) {
+  if (!lengths1 && !lengths2)
+    return approxmatch<false>(xyz1, xyz2, nullptr, nullptr, B, n, m, match, temp, stream);
+  return approxmatch<true>(xyz1, xyz2, lengths1, lengths2, B, n, m, match, temp, stream);
+}
+
+extern "C" int pdr_emd_cost_ragged(const float* xyz1, const float* xyz2, const int64_t* lengths1,
+                                   const int64_t* lengths2, int B, int n, int m, float* cost,
+                                   float* temp, pdr_stream_t stream) {
+  if (!lengths1 && !lengths2)
+    return emd_cost<false>(xyz1, xyz2, nullptr, nullptr, B, n, m, cost, temp, stream);
+  return emd_cost<true>(xyz1, xyz2, lengths1, lengths2, B, n, m, cost, temp, stream);
+}
+
+extern "C" int pdr_matchcost_ragged(const float* xyz1, const float* xyz2, const int64_t* lengths1,
+                                    const int64_t* lengths2, const float* match, int B, int n, int m,
+                                    float* cost, float* temp, pdr_stream_t stream) {
+  if (!lengths1 && !lengths2)
+    return matchcost<false>(xyz1, xyz2, nullptr, nullptr, match, B, n, m, cost, temp, stream);
+  return matchcost<true>(xyz1, xyz2, lengths1, lengths2, match, B, n, m, cost, temp, stream);
+}
+
+extern "C" int pdr_matchcost_grad_ragged(const float* grad_cost, const float* xyz1, const float* xyz2,
+                                         const int64_t* lengths1, const int64_t* lengths2,
+                                         const float* match, int B, int n, int m, float* grad1,
+                                         float* grad2, pdr_stream_t stream) {
+  if (!lengths1 && !lengths2)
+    return matchcost_grad<false>(grad_cost, xyz1, xyz2, nullptr, nullptr, match, B, n, m, grad1, grad2,
+                                 stream);
+  return matchcost_grad<true>(grad_cost, xyz1, xyz2, lengths1, lengths2, match, B, n, m, grad1, grad2,
+                              stream);
 }

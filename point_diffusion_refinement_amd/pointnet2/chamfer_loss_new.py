@@ -11,6 +11,8 @@ length-aware knn_points with a gradient), reference :121-128, 152-155 semantics:
 points are not candidates and contribute 0.  pytorch3d `Pointclouds` objects are rejected.
 All distances are SQUARED; cd_p takes the square root per point before the mean;
 the F-score threshold is applied to squared distances.
+fscore / calc_cd / Chamfer_F1 take the lengths too: precision, recall and the means are over each cloud's valid
+points, and a cloud of length 0 yields 0 for every metric.
 """
 from typing import Union
 
@@ -162,17 +164,46 @@ def chamfer_distance(x, y, x_lengths=None, y_lengths=None, x_normals=None, y_nor
     return cham_x, cham_y, (norm_x + norm_y if with_normals else None)
 
 
-def fscore(dist1, dist2, threshold=0.0001):
-    """F-score of two (B,P) SQUARED nearest-neighbour distance maps at `threshold` (also squared)."""
-    p1 = torch.mean((dist1 < threshold).float(), dim=1)
-    p2 = torch.mean((dist2 < threshold).float(), dim=1)
+def _valid_mean(v, lengths):
+    """Mean of every row of v (B,P) over its first lengths[b] entries (None: all P); 0 for a length of 0.  Entries
+    beyond the length are not read into the sum, whatever they hold."""
+    if lengths is None:
+        return v.mean(1)
+    lengths = lengths.to(v.device).clamp(0, v.shape[1])
+    valid = torch.arange(v.shape[1], device=v.device)[None] < lengths[:, None]
+    return torch.where(valid, v, torch.zeros_like(v)).sum(1) / lengths.clamp(min=1).to(v.dtype)
+
+
+def fscore(dist1, dist2, threshold=0.0001, lengths1=None, lengths2=None):
+    """F-score of two (B,P) SQUARED nearest-neighbour distance maps at `threshold` (also squared).
+    lengths1 / lengths2 (B,): precision and recall over the first lengths[b] points of each map only (a padded point's
+    distance of 0 is not a hit); a cloud of length 0 has precision / recall / F-score 0."""
+    if lengths1 is None and lengths2 is None:
+        p1 = torch.mean((dist1 < threshold).float(), dim=1)
+        p2 = torch.mean((dist2 < threshold).float(), dim=1)
+    else:
+        p1 = _valid_mean((dist1 < threshold).float(), lengths1)
+        p2 = _valid_mean((dist2 < threshold).float(), lengths2)
     f = 2 * p1 * p2 / (p1 + p2)
     f[torch.isnan(f)] = 0
     return f, p1, p2
 
 
-def calc_cd(output, gt, calc_f1=False, f1_threshold=0.0001):
-    """cd_p = (mean sqrt d1 + mean sqrt d2)/2, cd_t = mean d1 + mean d2, with d1 = gt->output."""
+def calc_cd(output, gt, calc_f1=False, f1_threshold=0.0001, output_lengths=None, gt_lengths=None):
+    """cd_p = (mean sqrt d1 + mean sqrt d2)/2, cd_t = mean d1 + mean d2, with d1 = gt->output.
+    output_lengths / gt_lengths (B,): sample b is output[b, :output_lengths[b]] against gt[b, :gt_lengths[b]]; the
+    means are over the valid points, and a sample with an empty cloud gives 0 for every metric."""
+    if output_lengths is not None or gt_lengths is not None:
+        on = lambda l, ref: None if l is None else l.to(device=ref.device, dtype=torch.int64)
+        output_lengths, gt_lengths = on(output_lengths, output), on(gt_lengths, gt)
+        d1, d2, _ = chamfer_distance(gt, output, x_lengths=gt_lengths, y_lengths=output_lengths, batch_reduction=None,
+                                     point_reduction=None)
+        cd_p = (_valid_mean(torch.sqrt(d1), gt_lengths) + _valid_mean(torch.sqrt(d2), output_lengths)) / 2
+        cd_t = _valid_mean(d1, gt_lengths) + _valid_mean(d2, output_lengths)
+        if calc_f1:
+            f1, _, _ = fscore(d1, d2, threshold=f1_threshold, lengths1=gt_lengths, lengths2=output_lengths)
+            return cd_p, cd_t, f1
+        return cd_p, cd_t
     d1, d2, _ = chamfer_distance(gt, output, batch_reduction=None, point_reduction=None)
     cd_p = (torch.sqrt(d1).mean(1) + torch.sqrt(d2).mean(1)) / 2
     cd_t = d1.mean(1) + d2.mean(1)
@@ -187,5 +218,6 @@ class Chamfer_F1(nn.Module):
         super().__init__()
         self.f1_threshold = f1_threshold
 
-    def forward(self, xyz1, xyz2):
-        return calc_cd(xyz1, xyz2, calc_f1=True, f1_threshold=self.f1_threshold)
+    def forward(self, xyz1, xyz2, lengths1=None, lengths2=None):
+        return calc_cd(xyz1, xyz2, calc_f1=True, f1_threshold=self.f1_threshold, output_lengths=lengths1,
+                       gt_lengths=lengths2)

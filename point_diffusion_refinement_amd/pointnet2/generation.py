@@ -37,11 +37,12 @@ def batches(first, last, batch_size):
 
 
 def evaluate_batch(generate, condition, label, gt, scale=1.0, f1_threshold=1e-4, compute_emd=True, M_inv=None,
-                   translation=None):
+                   translation=None, gt_lengths=None):
     """One batch of the harness: `generate(condition, label)` -> (B,N,3) completed clouds.
     M_inv (B,3,3) / translation (B,1,3): the inverse of the augmentation the dataset applied to condition and gt
     (`augment_data_during_generation`, completion_eval.py:140-143): generated clouds and gt are mapped back with
     `matmul(x - translation, M_inv)` before anything is measured (:203-205).
+    gt_lengths (B,): gt is a padded batch, sample b being gt[b, :gt_lengths[b]] (the generated cloud is always full).
     Returns (generated/2/scale, records (B,5) = [cd_t, cd_p, f1, emd, label])."""
     from .chamfer_loss_new import calc_cd
     from .emd import earth_mover_distance
@@ -52,8 +53,12 @@ def evaluate_batch(generate, condition, label, gt, scale=1.0, f1_threshold=1e-4,
         gt = torch.matmul(gt - shift, M_inv)
     generated = generated / 2 / scale
     gt = gt / 2 / scale
-    cd_p, cd_t, f1 = calc_cd(generated, gt, calc_f1=True, f1_threshold=f1_threshold)
-    emd = earth_mover_distance(generated, gt) if compute_emd else torch.zeros_like(cd_t)
+    if gt_lengths is None:
+        cd_p, cd_t, f1 = calc_cd(generated, gt, calc_f1=True, f1_threshold=f1_threshold)
+        emd = earth_mover_distance(generated, gt) if compute_emd else torch.zeros_like(cd_t)
+    else:
+        cd_p, cd_t, f1 = calc_cd(generated, gt, calc_f1=True, f1_threshold=f1_threshold, gt_lengths=gt_lengths)
+        emd = earth_mover_distance(generated, gt, lengths2=gt_lengths) if compute_emd else torch.zeros_like(cd_t)
     rec = torch.stack([cd_t, cd_p, f1, emd, label.to(cd_t.dtype)], dim=1)
     return generated, rec
 
