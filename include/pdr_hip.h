@@ -439,7 +439,13 @@ int pdr_gn_fold(const float *part0, int ldp0, int tpb0, int C0, double mult0, co
                 int ldp1, int tpb1, int C1, double mult1, int B, int Cn, int G, double n, float eps,
                 const float *gamma, const float *beta, float *scale, float *shift, const int *nvalid0,
                 int tpb_main0, const int *nvalid1, int tpb_main1, pdr_stream_t stream);
-/* out (P,C; ld ldo) = prologue(X): materialise an activation descriptor */
+/* out (P,C; ld ldo >= C) = prologue(X): materialise an activation descriptor,
+ *     out[p, c] = post(pre(x[p, c]) * scale[b, c] + shift[b, c]) + add[b, c] + residual[p, c],  b = p / rows_per_batch,
+ * the product and the shift as one fused multiply-add, then one fp32 addition per present term, in this order; columns
+ * [C, ldo) of `out` are not touched.  Plain sources only (a gathered segment or residual: PDR_EUNSUPPORTED), row_div a
+ * power of two, segment widths summing to C.  The RESIDUAL is read as rseg.ptr[p * rseg.ld + c] for every column c of
+ * the C: only `ptr` and `ld` of rseg are consulted, its `C` and `row_div` are not (a residual is one row per position
+ * over all channels; a column offset goes into ptr). */
 int pdr_apply_act(const pdr_layer_in_t *in, long P, int C, float *out, int ldo,
                   pdr_stream_t stream);
 /* out (B,C) = max over the rows of every batch element of prologue(X) (plain sources, no residual): the global
@@ -451,12 +457,22 @@ int pdr_gn_finalize(const double *chan_stats, int B, int C, int Cn, int G, doubl
                     const float *gamma, const float *beta, float *scale, float *shift,
                     pdr_stream_t stream);
 /* out (B*m*K rows of leading dimension ldo >= Cs+3[+3][+3]) = [feats[idx] | rel | abs | centre];
- * feats (B,n,Cs) channel-last; columns beyond the row width are zero-filled */
+ * feats (B,n,Cs) channel-last (NULL when Cs == 0); columns beyond the row width are zero-filled, at most 8 of them
+ * (ldo - width > 8: PDR_EINVAL).  rel = xyz[b, idx] - new_xyz[b, j]; abs (with_abs) = xyz[b, idx]; centre
+ * (with_centre) = new_xyz[b, j].  patch_empty (needs counts): a query with counts[b, j] <= 0 gets a zero feature,
+ * rel = 0 and abs = its centre in all K slots (QueryAndGroup with subset=False); otherwise counts may be NULL and is
+ * not read. */
 int pdr_group_build(const float *feats, int Cs, const float *xyz, const float *new_xyz,
                     const int *idx, const int *counts, int B, int n, int m, int K,
                     int patch_empty, int with_abs, int with_centre, float *out, int ldo,
                     pdr_stream_t stream);
-/* out (B*n1*K rows, ld ldo >= C+11) = [feats_y[idx] | d2 | w | nn_abs | nn_rel | x]; idx int64 (B,n1,K) */
+/* out (B*n1*K rows, ld ldo) = [feats_y[idx] | d2 | w | nn_abs | nn_rel | x]; idx int64 (B,n1,K), d2 (B,n1,K) the
+ * squared distances of pdr_knn_points; feats_y (B,n2,C) channel-last (NULL when C == 0).
+ *   w[p] = (1/(d2[p]+1e-8)) / norm,  norm = sum over k = 0..K-1, in this order, of 1/(d2[b,i,k]+1e-8)   (fp32)
+ *   nn_abs = y[b, idx], nn_rel = nn_abs - x[b,i], x = x[b,i]; every other column is a copy.
+ * C+11 <= ldo <= C+11+8 (PDR_EINVAL otherwise); the columns [C+11, ldo) of every row are zero-filled, for every C.
+ * Every index must lie in [0, n2): the search must have been made with K <= n2 (pdr_knn_points pads K > n2 with
+ * idx -1, which this call would read out of bounds -- values are not inspected). */
 int pdr_knn_build(const float *feats_y, int C, const float *x, const float *y,
                   const long long *idx, const float *d2, int B, int n1, int n2, int K,
                   float *out, int ldo, pdr_stream_t stream);

@@ -49,7 +49,8 @@ __device__ __forceinline__ float activate(const pdr_layer_in_t& in, float x, flo
 }
 
 // out (P, C; ld ldo) = prologue(X): materialise an activation (needed where the next consumer
-// gathers whole feature rows, e.g. group_build / gather_rows)
+// gathers whole feature rows, e.g. group_build / gather_rows).  The residual is one row per position over all C
+// channels: rseg.ptr[row * rseg.ld + c] -- rseg.C and rseg.row_div are not consulted.  Columns [C, ldo) are left alone.
 __global__ __launch_bounds__(256) void apply_act_kernel(pdr_layer_in_t in, long P, int C,
                                                         float* __restrict__ out, int ldo) {
   const long e = static_cast<long>(blockIdx.x) * 256 + threadIdx.x;

@@ -38,7 +38,7 @@ __global__ __launch_bounds__(256) void group_build_kernel(
     const float* frow = feats + (static_cast<long>(b) * n + a) * Cs;
     float* orow = out + p * ldo;
     for (int c = lane; c < Cs; c += LPP) orow[c] = empty ? 0.0f : frow[c];
-    if (lane < ldo - Cout) orow[Cout + lane] = 0.0f;   // padding columns
+    for (int c = Cout + lane; c < ldo; c += LPP) orow[c] = 0.0f;   // padding columns, whatever LPP and ldo - Cout
     if (lane < Cout - Cs) {
       const int g = lane;                  // 0..2 rel, 3..5 abs|centre, 6..8 centre
       const int d = g % 3;
@@ -70,7 +70,7 @@ __global__ __launch_bounds__(256) void knn_build_kernel(
     const float* frow = feats_y + (static_cast<long>(b) * n2 + a) * C;
     float* orow = out + p * ldo;
     for (int c = lane; c < C; c += LPP) orow[c] = frow[c];
-    if (lane >= 11 && lane < 11 + ldo - Cout) orow[Cout + lane - 11] = 0.0f;   // padding columns
+    for (int c = Cout + lane; c < ldo; c += LPP) orow[c] = 0.0f;   // padding columns, whatever LPP and ldo - Cout
     if (lane < 11) {
       float v;
       if (lane == 0) {

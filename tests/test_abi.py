@@ -270,3 +270,59 @@ def test_round6_entry_points_validate_their_arguments_without_a_gpu():
     assert lib.pdr_fused_layer_pair(*args(li, li2)) == EUNSUP                  # a listed second problem
     assert lib.pdr_fused_layer_pair(None, 4096, C.byref(li2), 128, 64, 0x2000, 64, None, 64, 0x3000, 64, 0x4000, 64, None,
                                     None, 64, None) == EINVAL
+
+
+def test_activation_entry_points_refuse_what_they_do_not_carry_without_a_gpu():
+    """pdr_apply_act / pdr_act_colmax: gathered sources, a row_div that is no power of two, segment widths that do not
+    sum to C and (pdr_act_colmax) a residual, an output-side add or a ragged last cloud are return codes decided on the
+    host; nothing is launched."""
+    import ctypes as C
+    from point_diffusion_refinement_amd import _lib
+    lib = _lib.load()
+    EINVAL, EUNSUP = _lib.PDR_EINVAL, _lib.PDR_EUNSUPPORTED
+
+    def desc(widths=(24, 40), **k):
+        li = _lib.LayerIn()
+        li.n_seg = len(widths)
+        for i, w in enumerate(widths):
+            li.seg[i].ptr, li.seg[i].C, li.seg[i].ld, li.seg[i].row_div = 0x1000, w, 64, 1
+        li.rows_per_batch = 32
+        if "gV" in k:
+            li.seg[1].gV = k["gV"]
+        if "row_div" in k:
+            li.seg[0].row_div = k["row_div"]
+        if "rseg_gV" in k:
+            li.rseg.ptr, li.rseg.gV = 0x2000, k["rseg_gV"]
+        if "rseg" in k:
+            li.rseg.ptr, li.rseg.C, li.rseg.ld, li.rseg.row_div = k["rseg"], 64, 64, 1
+        if "oadd" in k:
+            li.oadd, li.oadd_ld, li.oadd_div = k["oadd"], 64, 8
+        return li
+
+    apply = lambda li, P=64: lib.pdr_apply_act(C.byref(li), P, 64, 0x3000, 64, None)
+    colmax = lambda li, P=64: lib.pdr_act_colmax(C.byref(li), P, 64, 0x3000, None)
+    for call in (apply, colmax):
+        assert call(desc(gV=0x4000)) == EUNSUP                     # a gathered segment
+        assert call(desc(row_div=3)) == EUNSUP
+        assert call(desc(widths=(24, 36))) == EINVAL               # 60 of the 64 channels
+        assert call(desc(widths=(24, 40, 8))) == EINVAL            # 72
+    assert apply(desc(rseg_gV=0x4000)) == EUNSUP                   # a gathered residual
+    assert colmax(desc(rseg=0x2000)) == EUNSUP
+    assert colmax(desc(oadd=0x2000)) == EUNSUP
+    assert colmax(desc(), P=80) == EINVAL                          # P is not a whole number of clouds
+
+
+def test_assembly_entry_points_validate_their_row_width_without_a_gpu():
+    """pdr_group_build / pdr_knn_build zero-fill at most 8 columns behind the row: ldo < width and ldo - width = 9 are
+    argument errors, as are patched empty balls without counts; pdr_pad_rows refuses ldo < C.  No launch."""
+    from point_diffusion_refinement_amd import _lib
+    lib = _lib.load()
+    p, EINVAL = 0x1000, _lib.PDR_EINVAL
+    gb = lambda ldo, counts=p, patch=0, flags=(1, 1): lib.pdr_group_build(p, 5, p, p, p, counts, 2, 10, 4, 2, patch,
+                                                                         flags[0], flags[1], p, ldo, None)
+    assert gb(13) == EINVAL and gb(14 + 9) == EINVAL               # 5 + 3 + 3 + 3 = 14 columns
+    assert gb(10, flags=(0, 1)) == EINVAL and gb(8 + 9, flags=(0, 0)) == EINVAL
+    assert gb(16, counts=None, patch=1) == EINVAL
+    kb = lambda ldo: lib.pdr_knn_build(p, 5, p, p, p, p, 2, 10, 12, 4, p, ldo, None)
+    assert kb(15) == EINVAL and kb(16 + 9) == EINVAL               # 5 + 11 = 16 columns
+    assert lib.pdr_pad_rows(p, 10, 8, p, 7, None) == EINVAL
