@@ -547,6 +547,29 @@ int pdr_gather_add_tiles_twin(const float *U, int ldu, int n_src, const float *V
                               int ldy, float *partial, int relu_col0, int ycol0, int ycols,
                               const unsigned char *tile_valid, int partial_tpb, const int *idx0, float *Yd, int ldyd,
                               const int *wrow0, float wmul, pdr_stream_t stream);
+/* The STATISTICS-ONLY pass of pdr_gather_add / _tiles / _tiles_twin (Y == NULL there) over one or two column windows
+ * [win0_col0, win0_col0 + win0_cols) and [win1_col0, win1_col0 + win1_cols) (win1_cols = 0: one window): ascending,
+ * disjoint, inside [0, Cout).  Only the windows' columns are gathered and reduced; their moments go to the same entries
+ * of `partial` as pdr_gather_add's, with the same bits, and every other entry of `partial` is left unwritten (the
+ * first conv of a grouped block is [first | residual | key]: no GroupNorm reads the residual window's moments).  The
+ * twin form writes Yd whole, as pdr_gather_add_tiles_twin.  PDR_EUNSUPPORTED when a window does not start on a
+ * multiple of 4 columns (use pdr_gather_add); PDR_EINVAL for windows that overlap, descend or leave [0, Cout), a NULL
+ * partial, and whatever pdr_gather_add rejects. */
+int pdr_gather_moments(const float *U, int ldu, int n_src, const float *V, const float *V0, int ldv,
+                       const int *idx, const int *counts, const float *s1, const float *r1,
+                       const float *s2, const float *r2, int B, int rows_per_batch, int K, int Cout,
+                       float *partial, int relu_col0, int win0_col0, int win0_cols, int win1_col0, int win1_cols,
+                       pdr_stream_t stream);
+int pdr_gather_moments_tiles(const float *U, int ldu, int n_src, const float *V, const float *V0, int ldv,
+                             const int *idx, const int *counts, const float *s1, const float *r1,
+                             const float *s2, const float *r2, int B, int rows_per_batch, int K, int Cout,
+                             float *partial, int relu_col0, int win0_col0, int win0_cols, int win1_col0,
+                             int win1_cols, const unsigned char *tile_valid, int partial_tpb, pdr_stream_t stream);
+int pdr_gather_moments_tiles_twin(const float *U, int ldu, int n_src, const float *V, const float *V0, int ldv,
+                                  const int *idx, const int *counts, int B, int rows_per_batch, int K, int Cout,
+                                  float *partial, int relu_col0, int win0_col0, int win0_cols, int win1_col0,
+                                  int win1_cols, const unsigned char *tile_valid, int partial_tpb, const int *idx0,
+                                  float *Yd, int ldyd, const int *wrow0, float wmul, pdr_stream_t stream);
 /* Moments of a materialised (B*rpb, C) tensor with one weight per row, appended to the moments of a tile subset:
  * partial row b*ptpb + tpb_full + j  <-  sum_r w[r] f, sum_r w[r] f^2 over the rows r of 128-row tile j of batch
  * element b (f = y, columns >= relu_col0: max(y,0)); partial rows b*ptpb + t (t < tpb_full) of the tiles with

@@ -82,6 +82,11 @@ SIGNATURES = {
     "pdr_gather_add": (_I, [_P, _I, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _I, _P, _I, _I, _I, _P]),
     "pdr_gather_add_tiles": (_I, [_P, _I, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _I, _P, _I, _I, _I,
                                   _P, _I, _P]),
+    "pdr_gather_moments": (_I, [_P, _I, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _I, _I, _I, _I, _I, _P]),
+    "pdr_gather_moments_tiles": (_I, [_P, _I, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _I, _I, _I, _I,
+                                      _I, _P, _I, _P]),
+    "pdr_gather_moments_tiles_twin": (_I, [_P, _I, _I, _P, _P, _I, _P, _P, _I, _I, _I, _I, _P, _I, _I, _I, _I, _I, _P,
+                                           _I, _P, _P, _I, _P, _F, _P]),
     "pdr_dedup_plan": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
     "pdr_dedup_sort": (_I, [_P, _I, _I, _P, _P, _P, _P]),
     "pdr_weighted_moments": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _I, _I, _P, _P]),

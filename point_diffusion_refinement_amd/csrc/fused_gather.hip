@@ -13,6 +13,8 @@
 //               weighted sum -> (B*npoint, D).
 // All tensors channel-LAST: a position's channels are contiguous, so neighbour feature rows are
 // read as whole contiguous segments and every store is coalesced.
+#include <type_traits>
+
 #include "pdr_common.h"
 
 namespace {
@@ -566,6 +568,230 @@ __global__ __launch_bounds__(256) void gather_add_kernel(
   }
 }
 
+// gather_moments: the STATISTICS-ONLY pass of a virtual first conv (Y == NULL) over the column windows whose moments a
+// GroupNorm reads -- [first C1 | residual Clast | key C2]: the residual window enters its consumer as a plain row-wise
+// add, nobody reads its moments, so no lane gathers or reduces it.  The float4 pieces of the windows form ONE index
+// space (piece q < w4a: window a, else window b), so a column pass has no idle range of lanes in its middle; the moments
+// go to the columns' ORIGINAL places in `partial`, every other entry stays unwritten.
+//
+// Same bits as gather_add_kernel<LPR, ...> for every kept column: LPR comes from the same Cout thresholds (host), so a
+// column's rows are dealt to the same (wave, row sub-group), accumulated in the same order and folded through the same
+// shuffle / LDS tree; only WHICH lane of a sub-group holds a column differs, which no sum depends on.  What the pass
+// no longer issues: the query row V[i] is loaded once per iteration of rows that belong to one query (3 of 4 loads of
+// the K = 8 form with 64 lanes per row, 31 of 32 of the K = 32 ball form), a row's index / kNN scalars are scalar
+// registers where a wave instruction covers one row, the ReLU v_max runs only in a column pass that reaches relu_col0,
+// and there is no Y window.  Adds / FMAs are written as float pairs (v_pk_add_f32 / v_pk_fma_f32: the same IEEE
+// operations; the compiler packs gather_add_kernel's scalar source the same way).  TWIN tiles (pdr_gather_moments_tiles_twin) keep gather_add_kernel's twin behaviour: they walk EVERY
+// column -- Yd is written whole, the per-query chain reads its residual columns -- and keep the windows' moments.
+typedef float pdr_f2 __attribute__((ext_vector_type(2)));
+
+template <int LPR, bool KPOW2, bool HAS_S, bool HAS_EM, bool TWIN>
+__device__ __forceinline__ void gather_moments_tile(
+    const float* __restrict__ U, int ldu, int n_src, const float* __restrict__ V, const float* __restrict__ V0, int ldv,
+    const int* __restrict__ idx, const int* __restrict__ counts, const float* __restrict__ s1,
+    const float* __restrict__ r1, const float* __restrict__ s2, const float* __restrict__ r2, int rows_per_batch_,
+    int K_, int Cout, float* __restrict__ partial, int relu_col0, const pdr::MomentWindows& mw,
+    const unsigned char* __restrict__ tile_valid, int partial_tpb, const pdr::GatherTwin& tw,
+    float (*red)[4 * LPR][2]) {
+  constexpr int TM = 128;
+  constexpr int RPI = 64 / LPR;            // rows per wave instruction
+  // row groups in flight per iteration, as gather_add_kernel (the order of a column's sum does not depend on it; 8 for
+  // LPR 64 measured 0-10 % slower than 4: DESIGN.md 4.11)
+  constexpr int DEPTH = 32 / RPI < 4 ? 32 / RPI : 4;
+  constexpr int CW = 4 * LPR;              // columns covered per pass
+  const int rows_per_batch = TWIN ? rows_per_batch_ / K_ : rows_per_batch_;
+  const int K = TWIN ? 1 : K_;
+  const int* __restrict__ idx_e = TWIN ? tw.idx0 : idx;
+  // (the wave number as a scalar: what depends on it alone -- nrows, the loop over the rows -- stays in scalar registers)
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int sub = lane / LPR, cl = lane % LPR;
+  // a per-row value held by lane `row` of the wave: with one row per wave instruction the row is uniform and the value
+  // a scalar (v_readlane: no LDS round trip, and the row's address arithmetic leaves the vector ALU)
+  auto row_value = [](int val, int row) {
+    if constexpr (RPI == 1) return __builtin_amdgcn_readlane(val, __builtin_amdgcn_readfirstlane(row));
+    else return __shfl(val, row, 64);
+  };
+  const int tpb = (rows_per_batch + TM - 1) / TM;
+  const int n_main = tw.n_main > 0 ? tw.n_main : static_cast<int>(gridDim.x);
+  const int bid = TWIN ? static_cast<int>(blockIdx.x) - n_main : pdr::xcd_contiguous(blockIdx.x, n_main);
+  const int b = bid / tpb, tb = bid - b * tpb;
+  if (!TWIN && tile_valid && !tile_valid[bid]) return;   // uniform
+  const int tpb_main = (rows_per_batch_ + TM - 1) / TM;
+  const long prow = static_cast<long>(b) * (partial_tpb > 0 ? partial_tpb : tpb) + (TWIN ? tpb_main : 0) + tb;
+  const long row0 = static_cast<long>(b) * rows_per_batch + static_cast<long>(tb) * TM;
+  const int nvalid = min(TM, rows_per_batch - tb * TM);
+  const int wlo = TWIN ? min(max(tw.wrow0[b] - tb * TM, 0), TM) : 0;   // uniform
+  const float* Ub = U + static_cast<long>(b) * n_src * ldu;
+  const int wr0 = wave * 32;
+  const int myr = min(wr0 + (lane & 31), nvalid - 1);
+  const long myp = row0 + myr;
+  const int my_idx = idx_e[myp];
+  const int my_empty = (HAS_EM && counts[myp / K] <= 0) ? 1 : 0;
+  const float my_s1 = (HAS_S && s1) ? s1[myp] : 0.0f;
+  const float my_s2 = (HAS_S && s2) ? s2[myp] : 0.0f;
+  const int nrows = max(0, min(32, nvalid - wr0));   // uniform
+  const int ksh = KPOW2 ? __builtin_ctz(K) : -1;
+  const long qbase = (row0 + wr0) / K;
+  const float* Vq = V + qbase * ldv;
+  const long v0d = HAS_EM ? V0 - V : 0;
+  // the walked columns as float4 pieces: [0, w4a) of window a, [w4a, w4) of window b (TWIN: every column)
+  const int wa0 = TWIN ? 0 : mw.c0a, wb0 = TWIN ? 0 : mw.c0b;
+  const int w4a = TWIN ? (Cout + 3) >> 2 : (mw.na + 3) >> 2;
+  const int w4 = w4a + (TWIN ? 0 : (mw.nb + 3) >> 2);
+  const int ea = mw.c0a + mw.na, eb = mw.c0b + mw.nb;     // window ends
+  for (int p0 = static_cast<int>(blockIdx.y) * LPR; p0 < w4; p0 += LPR * static_cast<int>(gridDim.y)) {
+    const int q = p0 + cl;
+    const bool cok = q < w4;
+    const int c = cok ? (q >= w4a ? wb0 + 4 * (q - w4a) : wa0 + 4 * q) : 0;
+    float4 q1 = make_float4(0, 0, 0, 0), q2 = make_float4(0, 0, 0, 0);
+    if (HAS_S && cok && r1) q1 = *reinterpret_cast<const float4*>(r1 + c);
+    if (HAS_S && cok && r2) q2 = *reinterpret_cast<const float4*>(r2 + c);
+    // columns ascend with the piece number: the pass reaches relu_col0 iff its last piece does (uniform)
+    const int ql = min(p0 + LPR, w4) - 1;
+    const bool relu = (ql >= w4a ? wb0 + 4 * (ql - w4a) : wa0 + 4 * ql) + 3 >= relu_col0;
+    float lo[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) lo[j] = (c + j >= relu_col0) ? 0.0f : -__builtin_inff();
+    pdr_f2 a1l = {0, 0}, a1h = {0, 0}, a2l = {0, 0}, a2h = {0, 0};
+    // One query row for a whole iteration when its DEPTH x RPI rows cannot straddle two queries (K a power of two >=
+    // that many rows; a wave's rows start on a multiple of K and nrows is one): V is loaded when r enters a new query
+    // and the empty-ball select is a scalar branch.  Else (K = 1 twin tiles, small or odd K) a V row per row, as
+    // gather_add_kernel.  SHARED / RELU are compile-time so that each form is a loop of its own (uniform choice).
+    auto walk_rows = [&](auto shared_tag, auto relu_tag) {
+      constexpr bool SHARED = decltype(shared_tag)::value, RELU = decltype(relu_tag)::value;
+      float4 vq = make_float4(0, 0, 0, 0);
+      int emq = 0;
+      for (int r = 0; r < nrows; r += DEPTH * RPI) {
+        float4 u[DEPTH], v[DEPTH];
+        float t1[DEPTH], t2[DEPTH];
+        int em[DEPTH], rr[DEPTH];
+#pragma unroll
+        for (int k = 0; k < DEPTH; ++k) {
+          rr[k] = r + k * RPI + sub;                               // this lane's row (per sub-group)
+          const int rc = min(rr[k], nrows - 1);
+          const int a = row_value(my_idx, rc);
+          if (HAS_S) {
+            t1[k] = __int_as_float(row_value(__float_as_int(my_s1), rc));
+            t2[k] = __int_as_float(row_value(__float_as_int(my_s2), rc));
+          }
+          u[k] = *reinterpret_cast<const float4*>(Ub + static_cast<unsigned>(a * ldu + c));
+          if (!SHARED) {
+            em[k] = HAS_EM ? row_value(my_empty, rc) : 0;
+            const float* vp;
+            if constexpr (KPOW2) vp = Vq + static_cast<unsigned>((rc >> ksh) * ldv + c);
+            else vp = V + ((row0 + wr0 + rc) / K) * ldv + c;
+            v[k] = *reinterpret_cast<const float4*>(vp + (em[k] ? v0d : 0));
+          }
+        }
+        // (behind the U loads: the first one of an iteration waits for nothing that is still in flight)
+        if constexpr (SHARED) if ((r & (K - 1)) == 0) {
+          emq = HAS_EM ? row_value(my_empty, r) : 0;
+          vq = *reinterpret_cast<const float4*>(Vq + static_cast<unsigned>((r >> ksh) * ldv + c) + (emq ? v0d : 0));
+        }
+#pragma unroll
+        for (int k = 0; k < DEPTH; ++k) {
+          if (rr[k] < nrows && cok) {
+            const float4 vv = SHARED ? vq : v[k];
+            pdr_f2 yl = {vv.x, vv.y}, yh = {vv.z, vv.w};
+            if (!HAS_EM || !(SHARED ? emq : em[k])) {
+              yl = pdr_f2{u[k].x, u[k].y} + yl;
+              yh = pdr_f2{u[k].z, u[k].w} + yh;
+              if (HAS_S) {
+                const pdr_f2 s1v = {t1[k], t1[k]}, s2v = {t2[k], t2[k]};
+                yl = __builtin_elementwise_fma(s1v, pdr_f2{q1.x, q1.y}, yl);
+                yh = __builtin_elementwise_fma(s1v, pdr_f2{q1.z, q1.w}, yh);
+                yl = __builtin_elementwise_fma(s2v, pdr_f2{q2.x, q2.y}, yl);
+                yh = __builtin_elementwise_fma(s2v, pdr_f2{q2.z, q2.w}, yh);
+              }
+            }
+            if (TWIN)
+              *reinterpret_cast<float4*>(tw.Y + (row0 + wr0 + rr[k]) * tw.ldy + c) = make_float4(yl.x, yl.y, yh.x, yh.y);
+            if (!TWIN || wr0 + rr[k] >= wlo) {
+              if (RELU) {
+                const float e[4] = {yl.x, yl.y, yh.x, yh.y};
+                float f[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                  asm("v_max_f32 %0, %1, %2" : "=v"(f[j]) : "v"(e[j]), "v"(lo[j]));   // max(y, 0) or y (bound -inf)
+                yl = pdr_f2{f[0], f[1]};
+                yh = pdr_f2{f[2], f[3]};
+              }
+              a1l += yl;
+              a1h += yh;
+              a2l = __builtin_elementwise_fma(yl, yl, a2l);
+              a2h = __builtin_elementwise_fma(yh, yh, a2h);
+            }
+          }
+        }
+      }
+    };
+    bool shared = false;                                           // uniform
+    if constexpr (KPOW2 && !TWIN) {
+      shared = K >= DEPTH * RPI;
+      if (shared) {
+        if (relu) walk_rows(std::true_type{}, std::true_type{});
+        else walk_rows(std::true_type{}, std::false_type{});
+      }
+    }
+    if (!shared) {
+      if (relu) walk_rows(std::false_type{}, std::true_type{});
+      else walk_rows(std::false_type{}, std::false_type{});
+    }
+    // fold the RPI row sub-groups (lanes with equal `cl`), then the 4 waves through LDS: gather_add_kernel's tree
+    float a1[4] = {a1l.x, a1l.y, a1h.x, a1h.y}, a2[4] = {a2l.x, a2l.y, a2h.x, a2h.y};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+#pragma unroll
+      for (int off = LPR; off < 64; off <<= 1) {
+        a1[j] += __shfl_xor(a1[j], off, 64);
+        a2[j] += __shfl_xor(a2[j], off, 64);
+      }
+    }
+    if (sub == 0) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        red[wave][4 * cl + j][0] = a1[j];
+        red[wave][4 * cl + j][1] = a2[j];
+      }
+    }
+    __syncthreads();
+    const int t = static_cast<int>(threadIdx.x);
+    const int qq = p0 + (t >> 2);
+    if (t < CW && qq < w4) {
+      const int col = (qq >= w4a ? wb0 + 4 * (qq - w4a) : wa0 + 4 * qq) + (t & 3);
+      // a window's last piece may reach past its end; a twin tile walked the columns between the windows too
+      const bool keep = TWIN ? ((col >= mw.c0a && col < ea) || (col >= mw.c0b && col < eb)) : col < (qq >= w4a ? eb : ea);
+      if (keep) {
+        const float m1 = (red[0][t][0] + red[1][t][0]) + (red[2][t][0] + red[3][t][0]);
+        const float m2 = (red[0][t][1] + red[1][t][1]) + (red[2][t][1] + red[3][t][1]);
+        float* o = partial + (prow * Cout + col) * 2;
+        o[0] = TWIN ? m1 * tw.wmul : m1;
+        o[1] = TWIN ? m2 * tw.wmul : m2;
+      }
+    }
+    __syncthreads();
+  }
+}
+
+template <int LPR, bool KPOW2, bool HAS_S, bool HAS_EM>
+__global__ __launch_bounds__(256) void gather_moments_kernel(
+    const float* __restrict__ U, int ldu, int n_src, const float* __restrict__ V, const float* __restrict__ V0, int ldv,
+    const int* __restrict__ idx, const int* __restrict__ counts, const float* __restrict__ s1,
+    const float* __restrict__ r1, const float* __restrict__ s2, const float* __restrict__ r2, int rows_per_batch, int K,
+    int Cout, float* __restrict__ partial, int relu_col0, pdr::MomentWindows mw,
+    const unsigned char* __restrict__ tile_valid, int partial_tpb, pdr::GatherTwin tw) {
+  __shared__ float red[4][4 * LPR][2];
+  if constexpr (!HAS_S) {                  // (twin tiles exist in the ball form only)
+    if (tw.n_main > 0 && static_cast<int>(blockIdx.x) >= tw.n_main) {   // uniform
+      gather_moments_tile<LPR, KPOW2, false, HAS_EM, true>(U, ldu, n_src, V, V0, ldv, idx, counts, s1, r1, s2, r2, rows_per_batch,
+                                                   K, Cout, partial, relu_col0, mw, tile_valid, partial_tpb, tw, red);
+      return;
+    }
+  }
+  gather_moments_tile<LPR, KPOW2, HAS_S, HAS_EM, false>(U, ldu, n_src, V, V0, ldv, idx, counts, s1, r1, s2, r2, rows_per_batch, K,
+                                                Cout, partial, relu_col0, mw, tile_valid, partial_tpb, tw, red);
+}
+
 // Y (B*rows_per_batch, Cout; ld ldy) = U[b, idx[p]] + V[p / K] (+ s1[p] r1 + s2[p] r2), empty balls -> V0.
 // U (B, n_src, ldu), V / V0 (B*rows_per_batch/K, ldv); all leading dimensions multiples of 4, 16-B
 // aligned.  partial: NULL or (B * ceil(rows_per_batch / 128), Cout, 2) moments as in pdr_fused_layer.
@@ -629,6 +855,108 @@ static int gather_add_impl(const float* U, int ldu, int n_src, const float* V, c
 #undef PDR_GA
 #undef PDR_GA_K
   return pdr::check_launch();
+}
+
+// The statistics-only pass over one or two column windows (pdr_gather_moments*): gather_add_impl's argument rules, LPR
+// and grid, without a Y; win[1] < 1 columns: one window.
+static int gather_moments_impl(const float* U, int ldu, int n_src, const float* V, const float* V0, int ldv,
+                               const int* idx, const int* counts, const float* s1, const float* r1, const float* s2,
+                               const float* r2, int B, int rows_per_batch, int K, int Cout, float* partial,
+                               int relu_col0, int win0_col0, int win0_cols, int win1_col0, int win1_cols,
+                               const unsigned char* tile_valid, int partial_tpb, pdr_stream_t stream,
+                               const int* idx0 = nullptr, float* Yd = nullptr, int ldyd = 0,
+                               const int* wrow0 = nullptr, float wmul = 1.0f) {
+  if (!U || !V || !idx || !partial || B < 0 || rows_per_batch <= 0 || K <= 0 || Cout <= 0 || n_src <= 0)
+    return PDR_EINVAL;
+  // windows: inside [0, Cout), ascending, disjoint
+  if (win0_col0 < 0 || win0_cols <= 0 || win0_cols > Cout - win0_col0) return PDR_EINVAL;
+  if (win1_cols < 0 || (win1_cols > 0 && (win1_col0 < win0_col0 + win0_cols || win1_cols > Cout - win1_col0)))
+    return PDR_EINVAL;
+  if (B == 0) return PDR_OK;
+  if (rows_per_batch % K != 0 || (counts && !V0) || (s1 && !r1) || (s2 && !r2)) return PDR_EINVAL;
+  const int c4 = (Cout + 3) & ~3;
+  if (ldu % 4 || ldv % 4 || ldu < c4 || ldv < c4) return PDR_EINVAL;
+  auto al = [](const void* q) { return reinterpret_cast<uintptr_t>(q) % 16 == 0; };
+  if (!al(U) || !al(V) || (V0 && !al(V0)) || (r1 && !al(r1)) || (r2 && !al(r2))) return PDR_EINVAL;
+  const int tpb = (rows_per_batch + 127) / 128;
+  const bool kpow2 = (K & (K - 1)) == 0 && K <= 32;
+  const bool has_s = s1 != nullptr || s2 != nullptr;
+  pdr::GatherTwin tw{idx0, Yd, wrow0, ldyd, 0, wmul};
+  long nblocks = static_cast<long>(B) * tpb;
+  if (idx0) {
+    const int mq = rows_per_batch / K;
+    if (!Yd || !wrow0 || has_s || ldyd % 4 || ldyd < c4 || !al(Yd) || partial_tpb < tpb + (mq + 127) / 128)
+      return PDR_EINVAL;
+    tw.n_main = static_cast<int>(nblocks);
+    nblocks += static_cast<long>(B) * ((mq + 127) / 128);
+  }
+  if (nblocks >= (1L << 31)) return PDR_EINVAL;
+  // rows move as float4 pieces: a window starts on one (the caller keeps pdr_gather_add for the others)
+  if (win0_col0 % 4 || (win1_cols > 0 && win1_col0 % 4)) return PDR_EUNSUPPORTED;
+  const pdr::MomentWindows mw{win0_col0, win0_cols, win1_cols > 0 ? win1_col0 : win0_col0 + win0_cols,
+                              win1_cols > 0 ? win1_cols : 0};
+  // lanes per row from the FULL width, as gather_add_impl: what keeps the order of every column's sum
+  const int lpr = Cout <= 64 ? 16 : (Cout <= 128 ? 32 : 64);
+  const int w4 = (mw.na + 3) / 4 + (mw.nb + 3) / 4;
+  const int passes = (w4 + lpr - 1) / lpr;
+  const int ncb = (nblocks <= 1024 && passes > 1) ? passes : 1;
+  const dim3 grid(static_cast<unsigned>(nblocks), static_cast<unsigned>(ncb));
+  hipStream_t st = pdr::as_stream(stream);
+#define PDR_GM_E(LPR, KP, HS, HE)                                                                                     \
+  hipLaunchKernelGGL((gather_moments_kernel<LPR, KP, HS, HE>), grid, dim3(256), 0, st, U, ldu, n_src, V, V0, ldv, idx, \
+                     counts, s1, r1, s2, r2, rows_per_batch, K, Cout, partial, relu_col0, mw, tile_valid,             \
+                     partial_tpb, tw)
+#define PDR_GM_K(LPR, KP, HS)                 \
+  do {                                        \
+    if (counts) PDR_GM_E(LPR, KP, HS, true);  \
+    else PDR_GM_E(LPR, KP, HS, false);        \
+  } while (0)
+#define PDR_GM(LPR)                                       \
+  do {                                                    \
+    if (kpow2 && has_s) PDR_GM_K(LPR, true, true);        \
+    else if (kpow2) PDR_GM_K(LPR, true, false);           \
+    else if (has_s) PDR_GM_K(LPR, false, true);           \
+    else PDR_GM_K(LPR, false, false);                     \
+  } while (0)
+  if (lpr == 16) PDR_GM(16);
+  else if (lpr == 32) PDR_GM(32);
+  else PDR_GM(64);
+#undef PDR_GM
+#undef PDR_GM_K
+#undef PDR_GM_E
+  return pdr::check_launch();
+}
+
+extern "C" int pdr_gather_moments(const float* U, int ldu, int n_src, const float* V, const float* V0, int ldv,
+                                  const int* idx, const int* counts, const float* s1, const float* r1, const float* s2,
+                                  const float* r2, int B, int rows_per_batch, int K, int Cout, float* partial,
+                                  int relu_col0, int win0_col0, int win0_cols, int win1_col0, int win1_cols,
+                                  pdr_stream_t stream) {
+  return gather_moments_impl(U, ldu, n_src, V, V0, ldv, idx, counts, s1, r1, s2, r2, B, rows_per_batch, K, Cout, partial,
+                             relu_col0, win0_col0, win0_cols, win1_col0, win1_cols, nullptr, 0, stream);
+}
+
+extern "C" int pdr_gather_moments_tiles(const float* U, int ldu, int n_src, const float* V, const float* V0, int ldv,
+                                        const int* idx, const int* counts, const float* s1, const float* r1,
+                                        const float* s2, const float* r2, int B, int rows_per_batch, int K, int Cout,
+                                        float* partial, int relu_col0, int win0_col0, int win0_cols, int win1_col0,
+                                        int win1_cols, const unsigned char* tile_valid, int partial_tpb,
+                                        pdr_stream_t stream) {
+  if (!tile_valid || partial_tpb < (rows_per_batch + 127) / 128) return PDR_EINVAL;
+  return gather_moments_impl(U, ldu, n_src, V, V0, ldv, idx, counts, s1, r1, s2, r2, B, rows_per_batch, K, Cout, partial,
+                             relu_col0, win0_col0, win0_cols, win1_col0, win1_cols, tile_valid, partial_tpb, stream);
+}
+
+extern "C" int pdr_gather_moments_tiles_twin(const float* U, int ldu, int n_src, const float* V, const float* V0,
+                                             int ldv, const int* idx, const int* counts, int B, int rows_per_batch,
+                                             int K, int Cout, float* partial, int relu_col0, int win0_col0,
+                                             int win0_cols, int win1_col0, int win1_cols,
+                                             const unsigned char* tile_valid, int partial_tpb, const int* idx0,
+                                             float* Yd, int ldyd, const int* wrow0, float wmul, pdr_stream_t stream) {
+  if (!tile_valid || !idx0 || rows_per_batch <= 0 || K <= 0 || rows_per_batch % K != 0) return PDR_EINVAL;
+  return gather_moments_impl(U, ldu, n_src, V, V0, ldv, idx, counts, nullptr, nullptr, nullptr, nullptr, B,
+                             rows_per_batch, K, Cout, partial, relu_col0, win0_col0, win0_cols, win1_col0, win1_cols,
+                             tile_valid, partial_tpb, stream, idx0, Yd, ldyd, wrow0, wmul);
 }
 
 extern "C" int pdr_gather_add(const float* U, int ldu, int n_src, const float* V, const float* V0,

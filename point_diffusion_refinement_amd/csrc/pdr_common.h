@@ -62,6 +62,12 @@ struct GatherTwin {
   float wmul;          // weight of the counted rows (K)
 };
 
+// Column windows of pdr_gather_moments (fused_gather.hip): the statistics-only pass of a virtual first conv walks
+// [c0a, c0a + na) and, when nb > 0, [c0b, c0b + nb) -- ascending, disjoint, float4-aligned starts -- and no other column.
+struct MomentWindows {
+  int c0a, na, c0b, nb;
+};
+
 // Second problem of a PAIRED wave-specialised launch (fused_layer_ws.hip, round 6): the same layer (weights, bias, output
 // width) over another set of rows -- the per-QUERY rows of a deduplicated block beside the tile subset of its
 // per-neighbour rows -- computed by the workgroups gx .. gridDim.x - 1 of ONE launch instead of a launch of their own.

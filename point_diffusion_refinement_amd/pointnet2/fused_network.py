@@ -110,6 +110,10 @@ TWIN_STATS = True
 # ... and the pooled rows of the skipped tiles' queries written by the pooled launch (pdr_layer_in_t.patch_values)
 # instead of a pdr_patch_rows launch behind it.
 FUSED_PATCH = True
+# The statistics-only pass of a virtual first conv (pdr_gather_add with Y = NULL) walks only the column windows whose
+# moments a GroupNorm reads (pdr_gather_moments*): the first conv's own columns and the attention's key columns, not the
+# residual conv's window between them (22-33 % of the columns).  Same bits in the windows; False: the whole-width pass.
+MOMENT_WINDOWS = True
 # The query-independent half of the DECODER's feature-transfer blocks (first-conv statistics, shared MLP, value conv: it
 # needs coordinates, the static condition features and the step embeddings only) on the geometry stream once that
 # stream is done with the geometry (1.4 ms into the step), beside the encoder; the decoder then only runs the query /
@@ -1169,8 +1173,15 @@ class FusedMlp:
 
     def first_conv_args(self, rpb):
         """What a SplitFirstConv that stands for this MLP's first conv is called with: the residual conv's column
-        window and the first GroupNorm's fold request."""
-        return dict(res=(self.res_col0, self.Clast) if self.res_col0 is not None else None, fold=self.first_fold(rpb))
+        window, the first GroupNorm's fold request and the column windows whose moments are read at all -- [0, C1) by
+        first_fold / after_first, [extra_col0, Cout) as the `second` window of the attention's n1_fold
+        (FusedAttention.__call__: key_col0 = extra_col0, C2 = the key conv's width).  The residual window between them
+        enters the MLP as a row-wise add (cur.radd): no GroupNorm reads its moments."""
+        windows = [(0, self.C1)]
+        if self.first.Cout > self.extra_col0:
+            windows.append((self.extra_col0, self.first.Cout - self.extra_col0))
+        return dict(res=(self.res_col0, self.Clast) if self.res_col0 is not None else None, fold=self.first_fold(rpb),
+                    windows=tuple(windows))
 
     def after_first(self, first, P, B, rpb, bank, x=None, folded=None):
         """Everything behind the first conv, given its output and statistics (`first`, a FirstOut) and, when whoever
@@ -1457,11 +1468,18 @@ class SplitFirstConv:
         return V2
 
     def __call__(self, src_feats_cl, src_xyz, query_xyz, idx32, counts, K, relu_col0, s1=None, s2=None,
-                 virtual=False, res=None, U=None, V2=None, fold=None, dd=None):
+                 virtual=False, res=None, U=None, V2=None, fold=None, dd=None, windows=None):
         """-> (first, folded).  first = a FirstOut with this conv's statistics: over the (B*m*K, ld) output, or with
         virtual=True in the form that consumers read as a gathered source (only the GroupNorm moments are computed
         here).  fold: FoldReq of the GroupNorm behind this conv; folded = a thunk launching that fold -> (scale, shift),
-        None without request."""
+        None without request.
+        windows: one or two (col0, cols) -- the only columns whose moments anyone reads (FusedMlp.first_conv_args).  A
+        statistics-only pass (virtual, nothing written) then leaves the other columns of `partial` UNWRITTEN
+        (MOMENT_WINDOWS).  Every reader of a virtual first conv's statistics stays inside the windows: Stats.window is
+        called by FoldReq.launch (first_fold: [0, C1)), FusedMlp.after_first ([0, C1)) and FusedAttention.__call__
+        (the key window [extra_col0, Cout)); Dedup.moments (TWIN_STATS = False) WRITES rows of `partial`, all columns,
+        and reads none; _stats_rows / _launch_pair lay out the statistics of the layer launches BEHIND the first conv,
+        not these; tools/kernel_roofline.py counts bytes from the arguments and does not read `partial`."""
         lib = _lib.load()
         B, n, Cs = src_feats_cl.shape
         m = query_xyz.shape[1]
@@ -1485,7 +1503,44 @@ class SplitFirstConv:
         partial = torch.empty((B * ptpb, self.Cout, 2), dtype=torch.float32, device=U.device)
         cptr = counts.data_ptr() if has_v0 else None
 
+        def gather_moments():
+            """The statistics-only pass over `windows` -> (done, Yd); done False: not carried, use gather_add."""
+            w0, w1 = windows[0], (windows[1] if len(windows) > 1 else (0, 0))
+            tabs = (U.data_ptr(), ld, n, V2.data_ptr(), _ptr(V2, ld) if has_v0 else None, ldv, idx32.data_ptr(), cptr)
+            knn = (s1.data_ptr() if s1 is not None else None, self.r1.data_ptr() if s1 is not None else None,
+                   s2.data_ptr() if s2 is not None else None, self.r2.data_ptr() if s2 is not None else None)
+            tail = (partial.data_ptr(), relu_col0, w0[0], w0[1], w1[0], w1[1])
+            if dd is None:
+                rc = lib.pdr_gather_moments(*tabs, *knn, B, rpb, K, self.Cout, *tail, _stream())
+                if rc == _lib.PDR_EUNSUPPORTED:
+                    return False, None
+                _lib.check(rc, "gather_moments")
+                return True, None
+            Yd = torch.empty((B * m, ld), dtype=torch.float32, device=U.device)
+            if TWIN_STATS:
+                rc = lib.pdr_gather_moments_tiles_twin(
+                    *tabs, B, rpb, K, self.Cout, *tail, dd.tile_valid.data_ptr(), ptpb, dd.idx0.data_ptr(),
+                    Yd.data_ptr(), ld, dd.wrow0.data_ptr(), float(K), _stream())
+                if rc == _lib.PDR_EUNSUPPORTED:
+                    return False, None
+                _lib.check(rc, "gather_moments_tiles_twin")
+                sub[0] = (dd.nvalid[0], dd.tpb)
+                return True, Yd
+            rc = lib.pdr_gather_moments_tiles(*tabs, *knn, B, rpb, K, self.Cout, *tail, dd.tile_valid.data_ptr(), ptpb,
+                                              _stream())
+            if rc == _lib.PDR_EUNSUPPORTED:
+                return False, None
+            _lib.check(rc, "gather_moments_tiles")
+            _lib.check(lib.pdr_gather_add(*tabs[:6], dd.idx0.data_ptr(), cptr, None, None, None, None, B, m, 1,
+                                          self.Cout, Yd.data_ptr(), ld, None, relu_col0, 0, -1, _stream()), "gather_add")
+            dd.moments(Yd, self.Cout, relu_col0, partial)
+            return True, Yd
+
         def gather_add(y, ldy, ycol0, ycols):
+            if y is None and MOMENT_WINDOWS and windows:
+                done, Yd = gather_moments()
+                if done:
+                    return Yd
             args = (U.data_ptr(), ld, n, V2.data_ptr(), _ptr(V2, ld) if has_v0 else None, ldv, idx32.data_ptr(), cptr,
                     s1.data_ptr() if s1 is not None else None, self.r1.data_ptr() if s1 is not None else None,
                     s2.data_ptr() if s2 is not None else None, self.r2.data_ptr() if s2 is not None else None,

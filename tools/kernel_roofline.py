@@ -92,6 +92,12 @@ def _work(name, args, lib):
         byt = 4.0 * (B * n_src * Cout + (P // K) * Cout + P) + (4.0 * P * (ycols if ycols > 0 else Cout) if Y else 0.0)
         lpr = 16 if Cout <= 64 else (32 if Cout <= 128 else 64)
         return "gather_add_kernel<%d>" % lpr, 2.0 * P * Cout, byt
+    if name == "pdr_gather_moments":
+        # the statistics-only pass over its column windows: table + query rows of those columns + index, nothing written
+        n_src, B, rpb, K, Cout, cols = args[2], args[12], args[13], args[14], args[15], args[19] + max(args[21], 0)
+        P = B * rpb
+        lpr = 16 if Cout <= 64 else (32 if Cout <= 128 else 64)
+        return "gather_moments_kernel<%d>" % lpr, 2.0 * P * cols, 4.0 * (B * n_src * cols + (P // K) * cols + P)
     if name == "pdr_attention_pool":
         B, npoint, K, D = args[8], args[9], args[10], args[11]
         P = B * npoint * K
@@ -127,7 +133,7 @@ def _work(name, args, lib):
     return name.replace("pdr_", "") + " (C ABI)", 0.0, 0.0
 
 
-_TIMED = ("pdr_fused_layer", "pdr_fused_layer_f16x3", "pdr_fused_layer_pool", "pdr_gather_add", "pdr_attention_pool", "pdr_gn_fold", "pdr_apply_act", "pdr_gather_rows",
+_TIMED = ("pdr_fused_layer", "pdr_fused_layer_f16x3", "pdr_fused_layer_pool", "pdr_gather_add", "pdr_gather_moments", "pdr_attention_pool", "pdr_gn_fold", "pdr_apply_act", "pdr_gather_rows",
           "pdr_furthest_point_sampling", "pdr_ball_query", "pdr_knn_points", "pdr_group_build", "pdr_knn_build",
           "pdr_knn_weights", "pdr_pad_rows", "pdr_knn_group", "pdr_embed_linear", "pdr_reverse_step")
 
