@@ -60,7 +60,8 @@ typedef void *pdr_stream_t; /* hipStream_t */
  *                wrow0 / wmul / patch_values / patch_ld / patch_w before `reserved_`; round 6: pdr_layer_in_t.oadd_rows, probe_out is a 4-slot ring
  *                (int[16]), pdr_set_option replaces the environment knobs, pdr_point_chain / pdr_point_chain_plan /
  *                pdr_fused_layer_pair are new; pdr_knn_points_ragged / pdr_chamfer_nn_ragged are new; pdr_approxmatch_ragged /
- *                pdr_emd_cost_ragged / pdr_matchcost_ragged / pdr_matchcost_grad_ragged are new. */
+ *                pdr_emd_cost_ragged / pdr_matchcost_ragged / pdr_matchcost_grad_ragged are new; pdr_emd_cost_grad /
+ *                pdr_emd_cost_grad_ragged are new. */
 int pdr_version(void);
 /* last hip error string seen by this thread after a PDR_ELAUNCH ("" if none) */
 const char *pdr_last_error(void);
@@ -210,7 +211,11 @@ int pdr_knn_points_grad(const float *x, const float *y, const int64_t *idx,
  * allocates its own (B,2(n+m)) temp, :186).
  * pdr_emd_cost = matchcost(approxmatch()) without materialising the 4*B*n*m-byte
  * match matrix (what pointnet2/emd.py:12-16 needs when return_match=False and no
- * gradient is requested); cost is NOT yet divided by max(n,m). */
+ * gradient is requested); cost is NOT yet divided by max(n,m).
+ * pdr_approxmatch and pdr_emd_cost (and their _ragged forms) LEAVE in `temp` the per-level factors of the closed form
+ *     match[b,l,k] = sum_level exp(level * |xyz1_k - xyz2_l|^2) * ratioL[level][k] * ratioR[level][l]
+ * (10 * (n + m) floats per pair; the layout stays private).  This is a promise of the interface: pdr_emd_cost_grad
+ * below reads them, so a caller that wants gradients keeps that workspace untouched until then. */
 size_t pdr_emd_workspace_bytes(int B, int n, int m);       /* approxmatch, emd_cost */
 size_t pdr_matchcost_workspace_bytes(int B, int n, int m); /* matchcost */
 int pdr_approxmatch(const float *xyz1, const float *xyz2, int B, int n, int m,
@@ -223,7 +228,22 @@ int pdr_matchcost_grad(const float *grad_cost, const float *xyz1,
                        int m, float *grad1, float *grad2, pdr_stream_t stream);
 int pdr_emd_cost(const float *xyz1, const float *xyz2, int B, int n, int m,
                  float *cost, float *temp, pdr_stream_t stream);
-/* The four EMD calls with per-cloud lengths (the rules of pdr_knn_points_ragged: lengths1 / lengths2 are int64 arrays
+/* Matrix-free matchcost_backward: the gradients of pdr_matchcost_grad on the match of pdr_approxmatch, without a
+ * (B,m,n) matrix anywhere:
+ *     grad1[b,k,:] = grad_cost[b] * sum_l 2 * match[b,l,k] * (xyz1[b,k] - xyz2[b,l])
+ *     grad2[b,l,:] = grad_cost[b] * sum_k 2 * match[b,l,k] * (xyz2[b,l] - xyz1[b,k])
+ * with match[b,l,k] evaluated on the fly from the factors in `temp`, by the expression pdr_approxmatch writes the
+ * matrix with (same distance, same exp, levels summed in the same order): every pair contributes the value the matrix
+ * would have held, and match is a constant of the differentiation, as in the reference (emd_kernel.cu:290-359).
+ * `temp` is the workspace of pdr_emd_workspace_bytes(B,n,m) bytes that a preceding pdr_emd_cost[_ragged] or
+ * pdr_approxmatch[_ragged] call on the SAME xyz1, xyz2, lengths, B, n and m left behind; it is only read, so one forward
+ * serves any number of these calls.  Sums run sequentially over the opposite index and nothing is atomic: the same
+ * input gives the same bits.  grad1 agrees bit for bit with pdr_matchcost_grad on that matrix; grad2 sums in index
+ * order where pdr_matchcost_grad sums by lanes.  Two launches on `stream`, no allocation, no synchronisation
+ * (capturable).  Validation and return codes are pdr_matchcost_grad's (B == 0: PDR_OK, nothing done). */
+int pdr_emd_cost_grad(const float *grad_cost, const float *xyz1, const float *xyz2, const float *temp,
+                      int B, int n, int m, float *grad1, float *grad2, pdr_stream_t stream);
+/* The EMD calls with per-cloud lengths (the rules of pdr_knn_points_ragged: lengths1 / lengths2 are int64 arrays
  * of B entries in DEVICE memory, read by the kernels only and clamped there to [0, n] / [0, m]; the host never reads
  * them, so the calls neither synchronise nor allocate, stay capturable, and a replayed graph follows the lengths then
  * in memory; NULL = every cloud is full).  Cloud b is the pair xyz1[b, :n_b], xyz2[b, :m_b] with n_b = lengths1[b],
@@ -251,6 +271,12 @@ int pdr_matchcost_grad_ragged(const float *grad_cost, const float *xyz1, const f
                               float *grad2, pdr_stream_t stream);
 int pdr_emd_cost_ragged(const float *xyz1, const float *xyz2, const int64_t *lengths1, const int64_t *lengths2,
                         int B, int n, int m, float *cost, float *temp, pdr_stream_t stream);
+/* pdr_emd_cost_grad under the same rules: rows at or beyond a cloud's length are never loaded (coordinates or
+ * factors), never candidates, and get gradient exactly 0; an empty pair gets all-zero gradients; `temp` comes from a
+ * preceding _ragged forward with the same lengths.  Two NULL length pointers: this IS pdr_emd_cost_grad. */
+int pdr_emd_cost_grad_ragged(const float *grad_cost, const float *xyz1, const float *xyz2,
+                             const int64_t *lengths1, const int64_t *lengths2, const float *temp,
+                             int B, int n, int m, float *grad1, float *grad2, pdr_stream_t stream);
 
 /* ==== fused channel-LAST layer kernels ========================================
  * These have no single pybind counterpart: each replaces a COMPOSITION of torch ops

@@ -50,6 +50,8 @@ SIGNATURES = {
     "pdr_matchcost_ragged": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P]),
     "pdr_matchcost_grad_ragged": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P]),
     "pdr_emd_cost_ragged": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P]),
+    "pdr_emd_cost_grad": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P]),
+    "pdr_emd_cost_grad_ragged": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P]),
     "pdr_fused_layer_tile_rows": (_I, [_I, _I]),
     "pdr_fused_layer_variant": (_I, [_I, _I]),
     "pdr_fused_layer_plan": (_I, [_P, _c.c_long, _I, _P, _I, _I, _P, _I, _P]),

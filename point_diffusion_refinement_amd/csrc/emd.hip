@@ -17,6 +17,8 @@
 //    operation order identical to the reference's `match += w`), and the cost-only
 //    path (pdr_emd_cost) never touches a matrix at all: 49 KB of traffic per pair
 //    instead of 350 MB.
+//  * the gradient needs no matrix either (pdr_emd_cost_grad, emd_cost_grad_kernel): the factors are still in the
+//    workspace when the forward returns, and each thread re-evaluates its row / column of match from them.
 //  * the opposite cloud streams through LDS as float4 {x,y,z,weight}; all lanes
 //    read the same address (broadcast).  Per-thread accumulation order over the
 //    opposite cloud is sequential, as in the reference, so the only numeric
@@ -429,6 +431,93 @@ __global__ __launch_bounds__(256) void matchcost_grad2_kernel(
   }
 }
 
+// Matrix-free matchcostgrad (pdr_emd_cost_grad): the two kernels above with match[l,k] evaluated on the fly from the
+// factors run_levels left in the workspace, by emd_match_kernel's expression (dx = xyz2 - xyz1, PDR_SUM3, __expf,
+// levels 0..9 in order, (exp * ratioL) * ratioR), so a pair contributes the value the matrix would have held.
+// SIDE 0: thread <-> xyz1 point k, xyz2 streamed (grad1); SIDE 1: thread <-> xyz2 point l, xyz1 streamed (grad2).
+// The own point's ten factors sit in registers; the opposite cloud streams through LDS in tiles of kGradTile points,
+// 64 bytes each {x,y,z,-}{f0..f3}{f4..f7}{f8,f9,-,-}, all lanes on one address.  Accumulation over the opposite index
+// is sequential from 0 and nothing is atomic: the result is a function of the input alone.  SIDE 0 is
+// matchcost_grad1_kernel's operation sequence; SIDE 1 sums in index order where matchcost_grad2_kernel sums by lanes.
+// RAGGED: as in the passes -- a padded own row walks the barriers and writes 0; a workgroup of padding loops 0 times;
+// the tile is filled below the opposite length only, coordinates and factors alike.
+constexpr int kGradTile = 256;
+template <bool RAGGED, int SIDE>
+__global__ __launch_bounds__(256) void emd_cost_grad_kernel(const float* __restrict__ grad_cost,
+                                                            const float* __restrict__ xyz1,
+                                                            const float* __restrict__ xyz2,
+                                                            const float* __restrict__ temp, int n, int m,
+                                                            float* __restrict__ grad,
+                                                            const int64_t* __restrict__ len1 = nullptr,
+                                                            const int64_t* __restrict__ len2 = nullptr) {
+  __shared__ float4 tile[kGradTile][4];
+  const int b = blockIdx.y;
+  const Ws w = ws_of(const_cast<float*>(temp), b, n, m);   // (read only)
+  const PairLen len = pair_len<RAGGED>(len1, len2, b, n, m);
+  const int nown = SIDE == 0 ? n : m, nopp = SIDE == 0 ? m : n;   // padded sizes = row strides
+  const int eown = SIDE == 0 ? len.n : len.m;
+  const int eopp = RAGGED && static_cast<int>(blockIdx.x) * 256 >= eown ? 0 : (SIDE == 0 ? len.m : len.n);
+  const float* pown = (SIDE == 0 ? xyz1 : xyz2) + static_cast<size_t>(b) * nown * 3;
+  const float* popp = (SIDE == 0 ? xyz2 : xyz1) + static_cast<size_t>(b) * nopp * 3;
+  const float* fown = SIDE == 0 ? w.ratioL : w.ratioR;
+  const float* fopp = SIDE == 0 ? w.ratioR : w.ratioL;
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  const bool valid = i < eown;
+  float xo = 0, yo = 0, zo = 0, fo[kLevels];
+#pragma unroll
+  for (int li = 0; li < kLevels; ++li) fo[li] = 0.0f;
+  if (valid) {
+    xo = pown[i * 3]; yo = pown[i * 3 + 1]; zo = pown[i * 3 + 2];
+#pragma unroll
+    for (int li = 0; li < kLevels; ++li) fo[li] = fown[static_cast<size_t>(li) * nown + i];
+  }
+  float gx = 0, gy = 0, gz = 0;
+  for (int j0 = 0; j0 < eopp; j0 += kGradTile) {
+    const int jend = (eopp - j0) < kGradTile ? (eopp - j0) : kGradTile;
+    __syncthreads();
+    if (static_cast<int>(threadIdx.x) < jend) {
+      const int j = j0 + threadIdx.x;
+      float f[kLevels];
+#pragma unroll
+      for (int li = 0; li < kLevels; ++li) f[li] = fopp[static_cast<size_t>(li) * nopp + j];
+      tile[threadIdx.x][0] = make_float4(popp[j * 3], popp[j * 3 + 1], popp[j * 3 + 2], 0.0f);
+      tile[threadIdx.x][1] = make_float4(f[0], f[1], f[2], f[3]);
+      tile[threadIdx.x][2] = make_float4(f[4], f[5], f[6], f[7]);
+      tile[threadIdx.x][3] = make_float4(f[8], f[9], 0.0f, 0.0f);
+    }
+    __syncthreads();
+    if (valid) {
+      for (int j = 0; j < jend; ++j) {
+        const float4 t = tile[j][0], a = tile[j][1], c = tile[j][2], e = tile[j][3];
+        const float ft[kLevels] = {a.x, a.y, a.z, a.w, c.x, c.y, c.z, c.w, e.x, e.y};
+        // xyz2 - xyz1 on both sides, as emd_match_kernel forms it
+        const float dx = SIDE == 0 ? t.x - xo : xo - t.x;
+        const float dy = SIDE == 0 ? t.y - yo : yo - t.y;
+        const float dz = SIDE == 0 ? t.z - zo : zo - t.z;
+        const float d2 = PDR_SUM3(dx, dy, dz);
+        float acc = 0.0f;
+#pragma unroll
+        for (int li = 0; li < kLevels; ++li) {
+          const float rl = SIDE == 0 ? fo[li] : ft[li], rr = SIDE == 0 ? ft[li] : fo[li];
+          acc += __expf(level_value(li) * d2) * rl * rr;
+        }
+        const float d = acc * 2;
+        gx += (xo - t.x) * d;
+        gy += (yo - t.y) * d;
+        gz += (zo - t.z) * d;
+      }
+    }
+  }
+  if (i >= nown) return;
+  float* o = grad + (static_cast<size_t>(b) * nown + i) * 3;
+  if (valid) {
+    const float g = grad_cost[b];
+    o[0] = gx * g; o[1] = gy * g; o[2] = gz * g;
+  } else if (RAGGED) {
+    o[0] = 0.0f; o[1] = 0.0f; o[2] = 0.0f;
+  }
+}
+
 // init + 10 levels of three passes: 31 launches over the padded sizes, with or without lengths
 template <bool RAGGED>
 int run_levels(const float* xyz1, const float* xyz2, const int64_t* len1, const int64_t* len2, int B,
@@ -506,6 +595,22 @@ int matchcost_grad(const float* grad_cost, const float* xyz1, const float* xyz2,
   return pdr::check_launch();
 }
 
+// `temp` holds the factors of a preceding approxmatch / emd_cost on the same clouds, lengths and sizes; read only
+template <bool RAGGED>
+int emd_cost_grad(const float* grad_cost, const float* xyz1, const float* xyz2, const int64_t* len1,
+                  const int64_t* len2, const float* temp, int B, int n, int m, float* grad1, float* grad2,
+                  pdr_stream_t stream) {
+  if (B < 0 || n <= 0 || m <= 0) return PDR_EINVAL;
+  if (B == 0) return PDR_OK;
+  if (!grad_cost || !xyz1 || !xyz2 || !temp || !grad1 || !grad2) return PDR_EINVAL;
+  hipStream_t s = pdr::as_stream(stream);
+  hipLaunchKernelGGL((emd_cost_grad_kernel<RAGGED, 0>), dim3((n + 255) / 256, B), dim3(256), 0, s, grad_cost,
+                     xyz1, xyz2, temp, n, m, grad1, len1, len2);
+  hipLaunchKernelGGL((emd_cost_grad_kernel<RAGGED, 1>), dim3((m + 255) / 256, B), dim3(256), 0, s, grad_cost,
+                     xyz1, xyz2, temp, n, m, grad2, len1, len2);
+  return pdr::check_launch();
+}
+
 }  // namespace
 
 extern "C" size_t pdr_emd_workspace_bytes(int B, int n, int m) {
@@ -575,4 +680,20 @@ extern "C" int pdr_matchcost_grad_ragged(const float* grad_cost, const float* xy
                                  stream);
   return matchcost_grad<true>(grad_cost, xyz1, xyz2, lengths1, lengths2, match, B, n, m, grad1, grad2,
                               stream);
+}
+
+// Matrix-free gradients of the cost from the workspace a preceding pdr_emd_cost[_ragged] / pdr_approxmatch[_ragged]
+// left behind (include/pdr_hip.h): no (B, m, n) matrix, two launches, capturable.
+extern "C" int pdr_emd_cost_grad(const float* grad_cost, const float* xyz1, const float* xyz2,
+                                 const float* temp, int B, int n, int m, float* grad1, float* grad2,
+                                 pdr_stream_t stream) {
+  return emd_cost_grad<false>(grad_cost, xyz1, xyz2, nullptr, nullptr, temp, B, n, m, grad1, grad2, stream);
+}
+
+extern "C" int pdr_emd_cost_grad_ragged(const float* grad_cost, const float* xyz1, const float* xyz2,
+                                        const int64_t* lengths1, const int64_t* lengths2, const float* temp,
+                                        int B, int n, int m, float* grad1, float* grad2, pdr_stream_t stream) {
+  if (!lengths1 && !lengths2)
+    return emd_cost_grad<false>(grad_cost, xyz1, xyz2, nullptr, nullptr, temp, B, n, m, grad1, grad2, stream);
+  return emd_cost_grad<true>(grad_cost, xyz1, xyz2, lengths1, lengths2, temp, B, n, m, grad1, grad2, stream);
 }

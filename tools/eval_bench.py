@@ -4,10 +4,17 @@
 
 Prints pairs/s for calc_cd (two K=1 nearest-neighbour searches, cd_p / cd_t / F1) and for the
 cost-only EMD path (pdr_emd_cost), the algorithmic rates behind them, and checks a few pairs against
-the CPU oracle (indices bit-exact, values 1e-4)."""
+the CPU oracle (indices bit-exact, values 1e-4).
+
+    python tools/eval_bench.py --emd-grad [--reps 5] [--commit HASH] [--out FILE]
+
+runs the differentiable-EMD leg instead: forward + backward of earth_mover_distance on the default path (materialised
+(B,m,n) match) and with matrix_free=True, wall time per iteration and the growth of torch.cuda.max_memory_allocated over
+one iteration, at (B, n, m) = (32, 2048, 2048), (4, 8192, 8192) and, matrix-free only, (2, 16384, 16384)."""
 import argparse
 import json
 import os
+import subprocess
 import sys
 import time
 
@@ -23,13 +30,83 @@ from point_diffusion_refinement_amd.pointnet2.chamfer_loss_new import calc_cd  #
 from point_diffusion_refinement_amd.pointnet2_ops import _ext  # noqa: E402
 
 
+EMD_GRAD_SHAPES = ((32, 2048, 2048, True), (4, 8192, 8192, True), (2, 16384, 16384, False))   # (..., default path too)
+
+
+def _commit():
+    try:
+        return subprocess.check_output(["git", "-C", ROOT, "rev-parse", "HEAD"], stderr=subprocess.DEVNULL,
+                                       text=True).strip()
+    except (OSError, subprocess.CalledProcessError):
+        return "unknown"
+
+
+def emd_grad_leg(dev, reps):
+    """[{B, n, m, path, ms_per_iter, peak_bytes, match_bytes}]: forward + backward, both clouds with a gradient."""
+    rows = []
+    for B, n, m, with_default in EMD_GRAD_SHAPES:
+        g = torch.Generator().manual_seed(n)
+        a = (torch.rand(B, n, 3, generator=g) - 0.5).to(dev).requires_grad_(True)
+        b = (torch.rand(B, m, 3, generator=g) - 0.5).to(dev).requires_grad_(True)
+        grads = {}
+        for path, kw in (("default", {}), ("matrix_free", {"matrix_free": True})):
+            if path == "default" and not with_default:
+                continue
+            row = {"B": B, "n": n, "m": m, "path": path, "match_bytes": 4 * B * n * m}
+
+            def step():
+                a.grad = b.grad = None
+                emd.earth_mover_distance(a, b, **kw).sum().backward()
+
+            try:
+                step()                                                   # warm-up: code objects, allocator
+                torch.cuda.synchronize()
+                torch.cuda.reset_peak_memory_stats(dev)
+                before = torch.cuda.memory_allocated(dev)
+                step()
+                torch.cuda.synchronize()
+                row["peak_bytes"] = torch.cuda.max_memory_allocated(dev) - before
+                t0 = time.perf_counter()
+                for _ in range(reps):
+                    step()
+                torch.cuda.synchronize()
+                row["ms_per_iter"] = round((time.perf_counter() - t0) / reps * 1e3, 3)
+                grads[path] = (a.grad.clone(), b.grad.clone())
+            except torch.cuda.OutOfMemoryError:
+                row["peak_bytes"] = row["ms_per_iter"] = None
+                row["note"] = "out of memory"
+            rows.append(row)
+            a.grad = b.grad = None
+            torch.cuda.empty_cache()
+        if len(grads) == 2:                                              # same gradients (tests hold them to a bar)
+            for u, v in zip(grads["default"], grads["matrix_free"]):
+                np.testing.assert_allclose(v.cpu().numpy(), u.cpu().numpy(), rtol=1e-3, atol=1e-5)
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--emd-grad", action="store_true", help="run the differentiable-EMD time / peak-memory leg only")
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--commit", default=None, help="recorded with --emd-grad (default: git rev-parse HEAD)")
+    ap.add_argument("--out", default=None, help="also write the --emd-grad result to this file")
     ap.add_argument("--pairs", type=int, default=10000)
     ap.add_argument("--batch", type=int, default=1000)
     ap.add_argument("--points", type=int, default=2048)
     args = ap.parse_args()
     dev = torch.device("cuda:0")
+    if args.emd_grad:
+        out = {"commit": args.commit or _commit(), "device": torch.cuda.get_device_name(dev), "reps": args.reps,
+               "what": "earth_mover_distance(a, b[, matrix_free=True]).sum().backward(), float32, both clouds with a "
+                       "gradient; ms_per_iter = host clock around reps iterations ending in a synchronise; peak_bytes "
+                       "= growth of torch.cuda.max_memory_allocated over one iteration",
+               "rows": emd_grad_leg(dev, args.reps)}
+        text = json.dumps(out, indent=1)
+        print(json.dumps(out))
+        if args.out:
+            with open(args.out, "w") as f:
+                f.write(text + "\n")
+        return
     g = torch.Generator().manual_seed(0)
     n = args.points
     a = (torch.rand(args.batch, n, 3, generator=g) - 0.5).to(dev)     # the /2/scale range of the harness
