@@ -389,7 +389,7 @@ extern "C" int pdr_gather_rows(const float* src, const int* idx, int B, int n, i
 }
 
 // ---------------------------------------------------------------------------------------------
-// gather_add: first 1x1 conv of a grouped block WITHOUT the grouped tensor.
+// gather_add / gather_moments: first 1x1 conv of a grouped block WITHOUT the grouped tensor.
 //
 // The grouped input of QueryAndGroup / group_knn is a gather of per-point rows plus per-query
 // terms, and the conv is linear, so for position p = (b, j, k) with neighbour a = idx[p]:
@@ -406,197 +406,68 @@ extern "C" int pdr_gather_rows(const float* src, const int* idx, int B, int n, i
 // One workgroup = 128 positions; each wave owns 32 CONSECUTIVE positions whose neighbour indices /
 // empty flags / per-position scalars are fetched with one coalesced load and then broadcast from
 // registers.  A row is covered by LPR lanes x float4 (LPR = 16 / 32 / 64 by output width), so a wave
-// instruction moves 64 / LPR rows and narrow outputs keep every lane busy; two row groups are in
-// flight per iteration.  Every U / V / Y access is a contiguous row segment.
-template <int LPR, bool KPOW2, bool HAS_S>
-__global__ __launch_bounds__(256) void gather_add_kernel(
-    const float* __restrict__ U, int ldu, int n_src, const float* __restrict__ V,
-    const float* __restrict__ V0, int ldv, const int* __restrict__ idx, const int* __restrict__ counts,
-    const float* __restrict__ s1, const float* __restrict__ r1, const float* __restrict__ s2,
-    const float* __restrict__ r2, int rows_per_batch_, int K_, int Cout, float* __restrict__ Y_, int ldy_,
-    float* __restrict__ partial, int relu_col0, int ycol0_, int ycol1_,
-    const unsigned char* __restrict__ tile_valid, int partial_tpb, pdr::GatherTwin tw) {
-  constexpr int TM = 128;
-  // TWIN blocks (blockIdx.x >= tw.n_main; round 5): the same sum over the block's per-QUERY rows -- neighbour = the
-  // query's first one (tw.idx0), K = 1 -- written whole to tw.Y, with the GroupNorm moments of the rows q >= wrow0[b]
-  // (the queries of the cloud's skipped tiles) times tw.wmul in partial row b partial_tpb + tiles_per_batch + tile:
-  // what a separate K = 1 launch + pdr_weighted_moments produced, in the launch that walks the tile subset.
-  const bool twin = static_cast<int>(blockIdx.x) >= tw.n_main && tw.n_main > 0;   // uniform
-  const int rows_per_batch = twin ? rows_per_batch_ / K_ : rows_per_batch_;
-  const int K = twin ? 1 : K_;
-  const int* __restrict__ idx_e = twin ? tw.idx0 : idx;
-  float* __restrict__ Y = twin ? tw.Y : Y_;
-  const int ldy = twin ? tw.ldy : ldy_;
-  const int ycol0 = twin ? 0 : ycol0_, ycol1 = twin ? ((Cout + 3) & ~3) : ycol1_;
-  constexpr int RPI = 64 / LPR;            // rows per wave instruction
-  // row groups in flight per iteration: the kernel is bound by the latency of its L2 gathers, so every wave keeps
-  // DEPTH x 2 independent 16-byte loads outstanding (4 measured against 2: see DESIGN.md)
-  constexpr int DEPTH = 32 / RPI < 4 ? 32 / RPI : 4;
-  constexpr int CW = 4 * LPR;              // columns covered per pass
-  __shared__ float red[4][CW][2];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int sub = lane / LPR, cl = lane % LPR;
-  const int tpb = (rows_per_batch + TM - 1) / TM;
-  const int n_main = tw.n_main > 0 ? tw.n_main : static_cast<int>(gridDim.x);
-  const int bid = twin ? static_cast<int>(blockIdx.x) - n_main : pdr::xcd_contiguous(blockIdx.x, n_main);
-  const int b = bid / tpb, tb = bid - b * tpb;
-  // a tile subset (pdr_dedup_plan): the other tiles are neither read nor written
-  if (!twin && tile_valid && !tile_valid[bid]) return;   // uniform
-  const int tpb_main = (rows_per_batch_ + TM - 1) / TM;
-  // the tile's partial row (twin tiles behind the cloud's main tiles)
-  const long prow = static_cast<long>(b) * (partial_tpb > 0 ? partial_tpb : tpb) + (twin ? tpb_main : 0) + tb;
-  const long row0 = static_cast<long>(b) * rows_per_batch + static_cast<long>(tb) * TM;
-  const int nvalid = min(TM, rows_per_batch - tb * TM);
-  // statistics: rows >= wlo of the tile count (twin: the queries behind the cloud's valid tiles), times wmul
-  const int wlo = twin ? min(max(tw.wrow0[b] - tb * TM, 0), TM) : 0;   // uniform
-  const float wmul = twin ? tw.wmul : 1.0f;
-  const float* Ub = U + static_cast<long>(b) * n_src * ldu;
-  const int wr0 = wave * 32;
-  const int myr = min(wr0 + (lane & 31), nvalid - 1);
-  const long myp = row0 + myr;
-  const int my_idx = idx_e[myp];
-  const int my_empty = (counts && counts[myp / K] <= 0) ? 1 : 0;
-  const float my_s1 = s1 ? s1[myp] : 0.0f;
-  const float my_s2 = s2 ? s2[myp] : 0.0f;
-  const int nrows = max(0, min(32, nvalid - wr0));   // uniform
-
-  // The kernel is VALU-issue bound (PMC: 35 VALU instructions per 16-byte gather before this rewrite, waves
-  // issue-stalled 47 % of their cycles), so the per-row work is kept minimal: the query row is an add + shift when
-  // K is a power of two that divides the wave's 32 rows (every shipped config; the general form is a 64-bit
-  // division per row group), the kNN terms and the empty-ball select exist only where their inputs do (uniform
-  // branches), the ReLU of the statistics is one v_max against a per-lane bound, addresses are 32-bit offsets.
-  constexpr bool has_s = HAS_S;                            // kNN terms d2 r1 + w r2 present
-  const bool has_em = counts != nullptr;                  // uniform
-  const int ksh = KPOW2 ? __builtin_ctz(K) : -1;          // KPOW2: K a power of two <= 32
-  const long qbase = (row0 + wr0) / K;                     // exact when ksh >= 0 (row0 + wr0 is a multiple of K)
-  const float* Vq = V + qbase * ldv;
-  const long v0d = has_em ? V0 - V : 0;                    // elements from V to V0 (same address space)
-  // (grid.y > 1, round 6: the column passes of a tile dealt to grid.y workgroups -- a launch of a few hundred tiles with
-  // a wide output (the first conv of the 16- / 64-point levels: 128-512 tiles x 1,100 columns) was a serial walk of five
-  // passes per wave on a half-empty chip)
-  for (int c0 = static_cast<int>(blockIdx.y) * CW; c0 < Cout; c0 += CW * static_cast<int>(gridDim.y)) {
-    const int c = c0 + 4 * cl;
-    const bool cok = c < Cout;   // row widths are padded to a multiple of 4 in ldu / ldv / ldy
-    const int cc = cok ? c : 0;
-    float4 q1 = make_float4(0, 0, 0, 0), q2 = make_float4(0, 0, 0, 0);
-    if (cok && r1) q1 = *reinterpret_cast<const float4*>(r1 + c);
-    if (cok && r2) q2 = *reinterpret_cast<const float4*>(r2 + c);
-    float lo[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) lo[j] = (c + j >= relu_col0) ? 0.0f : -__builtin_inff();
-    const bool ywin = Y && c >= ycol0 && c < ycol1;
-    float a1[4] = {0, 0, 0, 0}, a2[4] = {0, 0, 0, 0};
-    for (int r = 0; r < nrows; r += DEPTH * RPI) {
-      float4 u[DEPTH], v[DEPTH];
-      float t1[DEPTH], t2[DEPTH];
-      int em[DEPTH], rr[DEPTH];
-#pragma unroll
-      for (int k = 0; k < DEPTH; ++k) {
-        rr[k] = r + k * RPI + sub;                               // this lane's row (per sub-group)
-        const int rc = min(rr[k], nrows - 1);
-        const int a = __shfl(my_idx, rc, 64);
-        em[k] = has_em ? __shfl(my_empty, rc, 64) : 0;
-        if (has_s) {
-          t1[k] = __shfl(my_s1, rc, 64);
-          t2[k] = __shfl(my_s2, rc, 64);
-        }
-        u[k] = *reinterpret_cast<const float4*>(Ub + static_cast<unsigned>(a * ldu + cc));
-        const float* vp;
-        if constexpr (KPOW2) vp = Vq + static_cast<unsigned>((rc >> ksh) * ldv + cc);
-        else vp = V + ((row0 + wr0 + rc) / K) * ldv + cc;
-        v[k] = *reinterpret_cast<const float4*>(vp + (em[k] ? v0d : 0));
-      }
-#pragma unroll
-      for (int k = 0; k < DEPTH; ++k) {
-        if (rr[k] < nrows && cok) {
-          float4 y;
-          if (em[k]) {
-            y = v[k];
-          } else {
-            y = make_float4(u[k].x + v[k].x, u[k].y + v[k].y, u[k].z + v[k].z, u[k].w + v[k].w);
-            if (has_s) {
-              y.x = __builtin_fmaf(t1[k], q1.x, y.x); y.y = __builtin_fmaf(t1[k], q1.y, y.y);
-              y.z = __builtin_fmaf(t1[k], q1.z, y.z); y.w = __builtin_fmaf(t1[k], q1.w, y.w);
-              y.x = __builtin_fmaf(t2[k], q2.x, y.x); y.y = __builtin_fmaf(t2[k], q2.y, y.y);
-              y.z = __builtin_fmaf(t2[k], q2.z, y.z); y.w = __builtin_fmaf(t2[k], q2.w, y.w);
-            }
-          }
-          if (ywin) *reinterpret_cast<float4*>(Y + (row0 + wr0 + rr[k]) * ldy + (c - ycol0)) = y;
-          const float e[4] = {y.x, y.y, y.z, y.w};
-          if (wr0 + rr[k] >= wlo) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-              float f;
-              asm("v_max_f32 %0, %1, %2" : "=v"(f) : "v"(e[j]), "v"(lo[j]));   // max(y, 0) or y (bound -inf)
-              a1[j] += f;
-              a2[j] = __builtin_fmaf(f, f, a2[j]);
-            }
-          }
-        }
-      }
-    }
-    if (partial) {
-      // fold the RPI row sub-groups (lanes with equal `cl`), then the 4 waves through LDS
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-#pragma unroll
-        for (int off = LPR; off < 64; off <<= 1) {
-          a1[j] += __shfl_xor(a1[j], off, 64);
-          a2[j] += __shfl_xor(a2[j], off, 64);
-        }
-      }
-      if (sub == 0) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          red[wave][4 * cl + j][0] = a1[j];
-          red[wave][4 * cl + j][1] = a2[j];
-        }
-      }
-      __syncthreads();
-      const int cc2 = c0 + threadIdx.x;
-      if (threadIdx.x < CW && cc2 < Cout) {
-        const float t1 = (red[0][threadIdx.x][0] + red[1][threadIdx.x][0]) +
-                         (red[2][threadIdx.x][0] + red[3][threadIdx.x][0]);
-        const float t2 = (red[0][threadIdx.x][1] + red[1][threadIdx.x][1]) +
-                         (red[2][threadIdx.x][1] + red[3][threadIdx.x][1]);
-        float* o = partial + (prow * Cout + cc2) * 2;
-        o[0] = t1 * wmul;      // (x 1.0f outside the twin tiles: exact)
-        o[1] = t2 * wmul;
-      }
-      __syncthreads();
-    }
-  }
-}
-
-// gather_moments: the STATISTICS-ONLY pass of a virtual first conv (Y == NULL) over the column windows whose moments a
-// GroupNorm reads -- [first C1 | residual Clast | key C2]: the residual window enters its consumer as a plain row-wise
-// add, nobody reads its moments, so no lane gathers or reduces it.  The float4 pieces of the windows form ONE index
-// space (piece q < w4a: window a, else window b), so a column pass has no idle range of lanes in its middle; the moments
-// go to the columns' ORIGINAL places in `partial`, every other entry stays unwritten.
+// instruction moves 64 / LPR rows and narrow outputs keep every lane busy.  Every U / V / Y access is a
+// contiguous row segment.
 //
-// Same bits as gather_add_kernel<LPR, ...> for every kept column: LPR comes from the same Cout thresholds (host), so a
+// ONE body serves every entry point.  It walks one or two column WINDOWS of the output: pdr_gather_add* the single
+// window [0, Cout); pdr_gather_moments* -- the statistics-only pass of a virtual first conv -- the windows whose moments
+// a GroupNorm reads, [first C1 | . | key C2] of [first C1 | residual Clast | key C2]: the residual window enters its
+// consumer as a plain row-wise add, nobody reads its moments, so no lane gathers or reduces it.  The float4 pieces of the
+// windows form ONE index space (piece q < w4a: window a, else window b), so a column pass has no idle range of lanes in
+// its middle; the moments go to the columns' ORIGINAL places in `partial`, every other entry stays unwritten.
+//
+// A column's moments do not depend on the windows: LPR comes from the Cout thresholds (host) whatever is walked, so a
 // column's rows are dealt to the same (wave, row sub-group), accumulated in the same order and folded through the same
-// shuffle / LDS tree; only WHICH lane of a sub-group holds a column differs, which no sum depends on.  What the pass
-// no longer issues: the query row V[i] is loaded once per iteration of rows that belong to one query (3 of 4 loads of
-// the K = 8 form with 64 lanes per row, 31 of 32 of the K = 32 ball form), a row's index / kNN scalars are scalar
-// registers where a wave instruction covers one row, the ReLU v_max runs only in a column pass that reaches relu_col0,
-// and there is no Y window.  Adds / FMAs are written as float pairs (v_pk_add_f32 / v_pk_fma_f32: the same IEEE
-// operations; the compiler packs gather_add_kernel's scalar source the same way).  TWIN tiles (pdr_gather_moments_tiles_twin) keep gather_add_kernel's twin behaviour: they walk EVERY
-// column -- Yd is written whole, the per-query chain reads its residual columns -- and keep the windows' moments.
+// shuffle / LDS tree; only WHICH lane of a sub-group holds a column differs, which no sum depends on.
+//
+// The kernel is VALU-issue bound (PMC: 35 VALU instructions per 16-byte gather in its first form, waves issue-stalled
+// 47 % of their cycles), so the per-row work is kept minimal: the query row V[i] is loaded once per iteration of rows
+// that belong to one query (3 of 4 loads of the K = 8 form with 64 lanes per row, 31 of 32 of the K = 32 ball form), else
+// its address is an add + shift when K is a power of two that divides the wave's 32 rows (every shipped config; the
+// general form is a 64-bit division per row group); a row's index / kNN scalars are scalar registers where a wave
+// instruction covers one row; the kNN terms and the empty-ball select exist only in the instantiations that have their
+// inputs; the ReLU of the statistics is one v_max against a per-lane bound and runs only in a column pass that reaches
+// relu_col0; addresses are 32-bit offsets.  Adds / FMAs are written as float pairs (v_pk_add_f32 / v_pk_fma_f32).
+//
+// YWIN instantiations (pdr_gather_add* with a Y) also WRITE the columns [yw.c0, yw.c1) of the walked rows, at column
+// c - yw.c0 of Y, and allow partial == NULL (Y only: no accumulation, no fold, no barrier).  The flag is compile-time:
+// the statistics-only instantiations are on the step's critical path and carry no pointer, branch or register for it.
+//
+// TWIN tiles (blockIdx.x >= tw.n_main; pdr_gather_*_tiles_twin): the same sum over the block's per-QUERY rows --
+// neighbour = the query's first one (tw.idx0), K = 1 -- written whole to tw.Y (EVERY column: the per-query chain reads
+// its residual columns), with the GroupNorm moments of the rows q >= wrow0[b] (the queries of the cloud's skipped tiles)
+// times tw.wmul, on the windows' columns, in partial row b partial_tpb + tiles_per_batch + tile: what a separate K = 1
+// launch + pdr_weighted_moments produced, in the launch that walks the tile subset.
 typedef float pdr_f2 __attribute__((ext_vector_type(2)));
 
-template <int LPR, bool KPOW2, bool HAS_S, bool HAS_EM, bool TWIN>
-__device__ __forceinline__ void gather_moments_tile(
+template <bool YWIN>
+struct YWindow {};
+template <>
+struct YWindow<true> {
+  float* Y;            // (B rows_per_batch, ld): columns [c0, c1) of the output, from column 0 on
+  int ld, c0, c1;
+};
+
+template <bool YWIN>
+YWindow<YWIN> y_window(float* Y, int ld, int c0, int c1) {
+  if constexpr (YWIN) return {Y, ld, c0, c1};
+  else return {};
+}
+
+template <int LPR, bool KPOW2, bool HAS_S, bool HAS_EM, bool TWIN, bool YWIN>
+__device__ __forceinline__ void gather_tile(
     const float* __restrict__ U, int ldu, int n_src, const float* __restrict__ V, const float* __restrict__ V0, int ldv,
     const int* __restrict__ idx, const int* __restrict__ counts, const float* __restrict__ s1,
     const float* __restrict__ r1, const float* __restrict__ s2, const float* __restrict__ r2, int rows_per_batch_,
     int K_, int Cout, float* __restrict__ partial, int relu_col0, const pdr::MomentWindows& mw,
-    const unsigned char* __restrict__ tile_valid, int partial_tpb, const pdr::GatherTwin& tw,
+    const unsigned char* __restrict__ tile_valid, int partial_tpb, const pdr::GatherTwin& tw, const YWindow<YWIN>& yw,
     float (*red)[4 * LPR][2]) {
+  static_assert(!(TWIN && YWIN), "a twin tile writes tw.Y whole, never a window");
   constexpr int TM = 128;
   constexpr int RPI = 64 / LPR;            // rows per wave instruction
-  // row groups in flight per iteration, as gather_add_kernel (the order of a column's sum does not depend on it; 8 for
-  // LPR 64 measured 0-10 % slower than 4: DESIGN.md 4.11)
+  // row groups in flight per iteration: the kernel is bound by the latency of its L2 gathers, so every wave keeps
+  // DEPTH independent 16-byte U loads outstanding (4 measured against 2; the order of a column's sum does not depend on
+  // it; 8 for LPR 64 measured 0-10 % slower than 4: DESIGN.md 4.11)
   constexpr int DEPTH = 32 / RPI < 4 ? 32 / RPI : 4;
   constexpr int CW = 4 * LPR;              // columns covered per pass
   const int rows_per_batch = TWIN ? rows_per_batch_ / K_ : rows_per_batch_;
@@ -615,11 +486,14 @@ __device__ __forceinline__ void gather_moments_tile(
   const int n_main = tw.n_main > 0 ? tw.n_main : static_cast<int>(gridDim.x);
   const int bid = TWIN ? static_cast<int>(blockIdx.x) - n_main : pdr::xcd_contiguous(blockIdx.x, n_main);
   const int b = bid / tpb, tb = bid - b * tpb;
+  // a tile subset (pdr_dedup_plan): the other tiles are neither read nor written
   if (!TWIN && tile_valid && !tile_valid[bid]) return;   // uniform
   const int tpb_main = (rows_per_batch_ + TM - 1) / TM;
+  // the tile's partial row (twin tiles behind the cloud's main tiles)
   const long prow = static_cast<long>(b) * (partial_tpb > 0 ? partial_tpb : tpb) + (TWIN ? tpb_main : 0) + tb;
   const long row0 = static_cast<long>(b) * rows_per_batch + static_cast<long>(tb) * TM;
   const int nvalid = min(TM, rows_per_batch - tb * TM);
+  // statistics: rows >= wlo of the tile count (twin: the queries behind the cloud's valid tiles)
   const int wlo = TWIN ? min(max(tw.wrow0[b] - tb * TM, 0), TM) : 0;   // uniform
   const float* Ub = U + static_cast<long>(b) * n_src * ldu;
   const int wr0 = wave * 32;
@@ -630,18 +504,21 @@ __device__ __forceinline__ void gather_moments_tile(
   const float my_s1 = (HAS_S && s1) ? s1[myp] : 0.0f;
   const float my_s2 = (HAS_S && s2) ? s2[myp] : 0.0f;
   const int nrows = max(0, min(32, nvalid - wr0));   // uniform
-  const int ksh = KPOW2 ? __builtin_ctz(K) : -1;
-  const long qbase = (row0 + wr0) / K;
+  const int ksh = KPOW2 ? __builtin_ctz(K) : -1;          // KPOW2: K a power of two <= 32
+  const long qbase = (row0 + wr0) / K;                     // exact when ksh >= 0 (row0 + wr0 is a multiple of K)
   const float* Vq = V + qbase * ldv;
-  const long v0d = HAS_EM ? V0 - V : 0;
+  const long v0d = HAS_EM ? V0 - V : 0;                    // elements from V to V0 (same address space)
   // the walked columns as float4 pieces: [0, w4a) of window a, [w4a, w4) of window b (TWIN: every column)
   const int wa0 = TWIN ? 0 : mw.c0a, wb0 = TWIN ? 0 : mw.c0b;
   const int w4a = TWIN ? (Cout + 3) >> 2 : (mw.na + 3) >> 2;
   const int w4 = w4a + (TWIN ? 0 : (mw.nb + 3) >> 2);
   const int ea = mw.c0a + mw.na, eb = mw.c0b + mw.nb;     // window ends
+  // (grid.y > 1, round 6: the column passes of a tile dealt to grid.y workgroups -- a launch of a few hundred tiles with
+  // a wide output (the first conv of the 16- / 64-point levels: 128-512 tiles x 1,100 columns) was a serial walk of five
+  // passes per wave on a half-empty chip)
   for (int p0 = static_cast<int>(blockIdx.y) * LPR; p0 < w4; p0 += LPR * static_cast<int>(gridDim.y)) {
     const int q = p0 + cl;
-    const bool cok = q < w4;
+    const bool cok = q < w4;   // row widths are padded to a multiple of 4 in ldu / ldv / ldy
     const int c = cok ? (q >= w4a ? wb0 + 4 * (q - w4a) : wa0 + 4 * q) : 0;
     float4 q1 = make_float4(0, 0, 0, 0), q2 = make_float4(0, 0, 0, 0);
     if (HAS_S && cok && r1) q1 = *reinterpret_cast<const float4*>(r1 + c);
@@ -652,13 +529,16 @@ __device__ __forceinline__ void gather_moments_tile(
     float lo[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) lo[j] = (c + j >= relu_col0) ? 0.0f : -__builtin_inff();
+    bool ywin = false;
+    if constexpr (YWIN) ywin = c >= yw.c0 && c < yw.c1;
     pdr_f2 a1l = {0, 0}, a1h = {0, 0}, a2l = {0, 0}, a2h = {0, 0};
     // One query row for a whole iteration when its DEPTH x RPI rows cannot straddle two queries (K a power of two >=
     // that many rows; a wave's rows start on a multiple of K and nrows is one): V is loaded when r enters a new query
-    // and the empty-ball select is a scalar branch.  Else (K = 1 twin tiles, small or odd K) a V row per row, as
-    // gather_add_kernel.  SHARED / RELU are compile-time so that each form is a loop of its own (uniform choice).
-    auto walk_rows = [&](auto shared_tag, auto relu_tag) {
+    // and the empty-ball select is a scalar branch.  Else (K = 1 twin tiles, small or odd K) a V row per row.  SHARED,
+    // RELU and STATS (false: Y only) are compile-time so that each form is a loop of its own (uniform choice).
+    auto walk_rows = [&](auto shared_tag, auto relu_tag, auto stats_tag) {
       constexpr bool SHARED = decltype(shared_tag)::value, RELU = decltype(relu_tag)::value;
+      constexpr bool STATS = decltype(stats_tag)::value;
       float4 vq = make_float4(0, 0, 0, 0);
       int emq = 0;
       for (int r = 0; r < nrows; r += DEPTH * RPI) {
@@ -706,7 +586,12 @@ __device__ __forceinline__ void gather_moments_tile(
             }
             if (TWIN)
               *reinterpret_cast<float4*>(tw.Y + (row0 + wr0 + rr[k]) * tw.ldy + c) = make_float4(yl.x, yl.y, yh.x, yh.y);
-            if (!TWIN || wr0 + rr[k] >= wlo) {
+            if constexpr (YWIN) {
+              if (ywin)
+                *reinterpret_cast<float4*>(yw.Y + (row0 + wr0 + rr[k]) * yw.ld + (c - yw.c0)) =
+                    make_float4(yl.x, yl.y, yh.x, yh.y);
+            }
+            if (STATS && (!TWIN || wr0 + rr[k] >= wlo)) {
               if (RELU) {
                 const float e[4] = {yl.x, yl.y, yh.x, yh.y};
                 float f[4];
@@ -726,18 +611,25 @@ __device__ __forceinline__ void gather_moments_tile(
       }
     };
     bool shared = false;                                           // uniform
+    if constexpr (KPOW2 && !TWIN) shared = K >= DEPTH * RPI;
+    if constexpr (YWIN) {
+      if (!partial) {              // Y only: nothing is accumulated, folded or waited for (uniform: no barrier is missed)
+        if (!shared) walk_rows(std::false_type{}, std::false_type{}, std::false_type{});
+        if constexpr (KPOW2) if (shared) walk_rows(std::true_type{}, std::false_type{}, std::false_type{});
+        continue;
+      }
+    }
     if constexpr (KPOW2 && !TWIN) {
-      shared = K >= DEPTH * RPI;
       if (shared) {
-        if (relu) walk_rows(std::true_type{}, std::true_type{});
-        else walk_rows(std::true_type{}, std::false_type{});
+        if (relu) walk_rows(std::true_type{}, std::true_type{}, std::true_type{});
+        else walk_rows(std::true_type{}, std::false_type{}, std::true_type{});
       }
     }
     if (!shared) {
-      if (relu) walk_rows(std::false_type{}, std::true_type{});
-      else walk_rows(std::false_type{}, std::false_type{});
+      if (relu) walk_rows(std::false_type{}, std::true_type{}, std::true_type{});
+      else walk_rows(std::false_type{}, std::false_type{}, std::true_type{});
     }
-    // fold the RPI row sub-groups (lanes with equal `cl`), then the 4 waves through LDS: gather_add_kernel's tree
+    // fold the RPI row sub-groups (lanes with equal `cl`), then the 4 waves through LDS
     float a1[4] = {a1l.x, a1l.y, a1h.x, a1h.y}, a2[4] = {a2l.x, a2l.y, a2h.x, a2h.y};
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -773,37 +665,44 @@ __device__ __forceinline__ void gather_moments_tile(
   }
 }
 
-template <int LPR, bool KPOW2, bool HAS_S, bool HAS_EM>
-__global__ __launch_bounds__(256) void gather_moments_kernel(
+template <int LPR, bool KPOW2, bool HAS_S, bool HAS_EM, bool YWIN>
+__global__ __launch_bounds__(256) void gather_kernel(
     const float* __restrict__ U, int ldu, int n_src, const float* __restrict__ V, const float* __restrict__ V0, int ldv,
     const int* __restrict__ idx, const int* __restrict__ counts, const float* __restrict__ s1,
     const float* __restrict__ r1, const float* __restrict__ s2, const float* __restrict__ r2, int rows_per_batch, int K,
     int Cout, float* __restrict__ partial, int relu_col0, pdr::MomentWindows mw,
-    const unsigned char* __restrict__ tile_valid, int partial_tpb, pdr::GatherTwin tw) {
+    const unsigned char* __restrict__ tile_valid, int partial_tpb, pdr::GatherTwin tw, YWindow<YWIN> yw) {
   __shared__ float red[4][4 * LPR][2];
   if constexpr (!HAS_S) {                  // (twin tiles exist in the ball form only)
     if (tw.n_main > 0 && static_cast<int>(blockIdx.x) >= tw.n_main) {   // uniform
-      gather_moments_tile<LPR, KPOW2, false, HAS_EM, true>(U, ldu, n_src, V, V0, ldv, idx, counts, s1, r1, s2, r2, rows_per_batch,
-                                                   K, Cout, partial, relu_col0, mw, tile_valid, partial_tpb, tw, red);
+      gather_tile<LPR, KPOW2, false, HAS_EM, true, false>(U, ldu, n_src, V, V0, ldv, idx, counts, s1, r1, s2, r2,
+                                                          rows_per_batch, K, Cout, partial, relu_col0, mw, tile_valid,
+                                                          partial_tpb, tw, YWindow<false>{}, red);
       return;
     }
   }
-  gather_moments_tile<LPR, KPOW2, HAS_S, HAS_EM, false>(U, ldu, n_src, V, V0, ldv, idx, counts, s1, r1, s2, r2, rows_per_batch, K,
-                                                Cout, partial, relu_col0, mw, tile_valid, partial_tpb, tw, red);
+  gather_tile<LPR, KPOW2, HAS_S, HAS_EM, false, YWIN>(U, ldu, n_src, V, V0, ldv, idx, counts, s1, r1, s2, r2, rows_per_batch,
+                                                      K, Cout, partial, relu_col0, mw, tile_valid, partial_tpb, tw, yw, red);
 }
 
-// Y (B*rows_per_batch, Cout; ld ldy) = U[b, idx[p]] + V[p / K] (+ s1[p] r1 + s2[p] r2), empty balls -> V0.
-// U (B, n_src, ldu), V / V0 (B*rows_per_batch/K, ldv); all leading dimensions multiples of 4, 16-B
-// aligned.  partial: NULL or (B * ceil(rows_per_batch / 128), Cout, 2) moments as in pdr_fused_layer.
-static int gather_add_impl(const float* U, int ldu, int n_src, const float* V, const float* V0,
-                           int ldv, const int* idx, const int* counts, const float* s1,
-                           const float* r1, const float* s2, const float* r2, int B,
-                           int rows_per_batch, int K, int Cout, float* Y, int ldy, float* partial,
-                           int relu_col0, int ycol0, int ycols, const unsigned char* tile_valid, int partial_tpb,
-                           pdr_stream_t stream, const int* idx0 = nullptr, float* Yd = nullptr, int ldyd = 0,
-                           const int* wrow0 = nullptr, float wmul = 1.0f) {
-  if (!U || !V || !idx || (!Y && !partial) || B < 0 || rows_per_batch <= 0 || K <= 0 || Cout <= 0 ||
-      n_src <= 0)
+// The one launch path of pdr_gather_add* / pdr_gather_moments*.
+// Y (B*rows_per_batch, columns [ycol0, ycol0 + ycols) of Cout; ld ldy) = U[b, idx[p]] + V[p / K] (+ s1[p] r1 + s2[p] r2),
+// empty balls -> V0; NULL: statistics only.  U (B, n_src, ldu), V / V0 (B*rows_per_batch/K, ldv); all leading dimensions
+// multiples of 4, 16-B aligned.  partial: NULL (with a Y) or (B * ceil(rows_per_batch / 128), Cout, 2) moments as in
+// pdr_fused_layer, written on the columns of the windows [win0_col0, + win0_cols) and, with win1_cols > 0,
+// [win1_col0, + win1_cols): pdr_gather_add* passes the whole width.  Every return code is decided before the launch.
+static int gather_launch(const float* U, int ldu, int n_src, const float* V, const float* V0, int ldv, const int* idx,
+                         const int* counts, const float* s1, const float* r1, const float* s2, const float* r2, int B,
+                         int rows_per_batch, int K, int Cout, float* Y, int ldy, float* partial, int relu_col0, int ycol0,
+                         int ycols, int win0_col0, int win0_cols, int win1_col0, int win1_cols,
+                         const unsigned char* tile_valid, int partial_tpb, pdr_stream_t stream,
+                         const int* idx0 = nullptr, float* Yd = nullptr, int ldyd = 0, const int* wrow0 = nullptr,
+                         float wmul = 1.0f) {
+  if (!U || !V || !idx || (!Y && !partial) || B < 0 || rows_per_batch <= 0 || K <= 0 || Cout <= 0 || n_src <= 0)
+    return PDR_EINVAL;
+  // windows: inside [0, Cout), ascending, disjoint
+  if (win0_col0 < 0 || win0_cols <= 0 || win0_cols > Cout - win0_col0) return PDR_EINVAL;
+  if (win1_cols < 0 || (win1_cols > 0 && (win1_col0 < win0_col0 + win0_cols || win1_cols > Cout - win1_col0)))
     return PDR_EINVAL;
   if (B == 0) return PDR_OK;
   if (rows_per_batch % K != 0 || (counts && !V0) || (s1 && !r1) || (s2 && !r2)) return PDR_EINVAL;
@@ -818,7 +717,6 @@ static int gather_add_impl(const float* U, int ldu, int n_src, const float* V, c
   if (!al(U) || !al(V) || (V0 && !al(V0)) || (Y && !al(Y)) || (r1 && !al(r1)) || (r2 && !al(r2)))
     return PDR_EINVAL;
   const int tpb = (rows_per_batch + 127) / 128;
-  hipStream_t st = pdr::as_stream(stream);
   const bool kpow2 = (K & (K - 1)) == 0 && K <= 32;
   const bool has_s = s1 != nullptr || s2 != nullptr;
   pdr::GatherTwin tw{idx0, Yd, wrow0, ldyd, 0, wmul};
@@ -833,97 +731,46 @@ static int gather_add_impl(const float* U, int ldu, int n_src, const float* V, c
     nblocks += static_cast<long>(B) * ((mq + 127) / 128);
   }
   if (nblocks >= (1L << 31)) return PDR_EINVAL;
-  // column passes per workgroup: all of them, unless the launch has fewer tiles than the chip holds workgroups
-  const int cw = Cout <= 64 ? 64 : (Cout <= 128 ? 128 : 256);
-  const int passes = (Cout + cw - 1) / cw;
-  const int ncb = (nblocks <= 1024 && passes > 1) ? passes : 1;
-  const dim3 grid(static_cast<unsigned>(nblocks), static_cast<unsigned>(ncb));
-#define PDR_GA_K(LPR, KP, HS)                                                                          \
-  hipLaunchKernelGGL((gather_add_kernel<LPR, KP, HS>), grid, dim3(256), 0, st, U, ldu, n_src, V, V0, ldv, idx,  \
-                     counts, s1, r1, s2, r2, rows_per_batch, K, Cout, Y, ldy, partial, relu_col0, ycol0, \
-                     ycol0 + y4, tile_valid, partial_tpb, tw)
-#define PDR_GA(LPR)                                       \
-  do {                                                    \
-    if (kpow2 && has_s) PDR_GA_K(LPR, true, true);        \
-    else if (kpow2) PDR_GA_K(LPR, true, false);           \
-    else if (has_s) PDR_GA_K(LPR, false, true);           \
-    else PDR_GA_K(LPR, false, false);                     \
-  } while (0)
-  if (Cout <= 64) PDR_GA(16);
-  else if (Cout <= 128) PDR_GA(32);
-  else PDR_GA(64);
-#undef PDR_GA
-#undef PDR_GA_K
-  return pdr::check_launch();
-}
-
-// The statistics-only pass over one or two column windows (pdr_gather_moments*): gather_add_impl's argument rules, LPR
-// and grid, without a Y; win[1] < 1 columns: one window.
-static int gather_moments_impl(const float* U, int ldu, int n_src, const float* V, const float* V0, int ldv,
-                               const int* idx, const int* counts, const float* s1, const float* r1, const float* s2,
-                               const float* r2, int B, int rows_per_batch, int K, int Cout, float* partial,
-                               int relu_col0, int win0_col0, int win0_cols, int win1_col0, int win1_cols,
-                               const unsigned char* tile_valid, int partial_tpb, pdr_stream_t stream,
-                               const int* idx0 = nullptr, float* Yd = nullptr, int ldyd = 0,
-                               const int* wrow0 = nullptr, float wmul = 1.0f) {
-  if (!U || !V || !idx || !partial || B < 0 || rows_per_batch <= 0 || K <= 0 || Cout <= 0 || n_src <= 0)
-    return PDR_EINVAL;
-  // windows: inside [0, Cout), ascending, disjoint
-  if (win0_col0 < 0 || win0_cols <= 0 || win0_cols > Cout - win0_col0) return PDR_EINVAL;
-  if (win1_cols < 0 || (win1_cols > 0 && (win1_col0 < win0_col0 + win0_cols || win1_cols > Cout - win1_col0)))
-    return PDR_EINVAL;
-  if (B == 0) return PDR_OK;
-  if (rows_per_batch % K != 0 || (counts && !V0) || (s1 && !r1) || (s2 && !r2)) return PDR_EINVAL;
-  const int c4 = (Cout + 3) & ~3;
-  if (ldu % 4 || ldv % 4 || ldu < c4 || ldv < c4) return PDR_EINVAL;
-  auto al = [](const void* q) { return reinterpret_cast<uintptr_t>(q) % 16 == 0; };
-  if (!al(U) || !al(V) || (V0 && !al(V0)) || (r1 && !al(r1)) || (r2 && !al(r2))) return PDR_EINVAL;
-  const int tpb = (rows_per_batch + 127) / 128;
-  const bool kpow2 = (K & (K - 1)) == 0 && K <= 32;
-  const bool has_s = s1 != nullptr || s2 != nullptr;
-  pdr::GatherTwin tw{idx0, Yd, wrow0, ldyd, 0, wmul};
-  long nblocks = static_cast<long>(B) * tpb;
-  if (idx0) {
-    const int mq = rows_per_batch / K;
-    if (!Yd || !wrow0 || has_s || ldyd % 4 || ldyd < c4 || !al(Yd) || partial_tpb < tpb + (mq + 127) / 128)
-      return PDR_EINVAL;
-    tw.n_main = static_cast<int>(nblocks);
-    nblocks += static_cast<long>(B) * ((mq + 127) / 128);
-  }
-  if (nblocks >= (1L << 31)) return PDR_EINVAL;
-  // rows move as float4 pieces: a window starts on one (the caller keeps pdr_gather_add for the others)
+  // rows move as float4 pieces: a window starts on one (the caller keeps the whole width for the others)
   if (win0_col0 % 4 || (win1_cols > 0 && win1_col0 % 4)) return PDR_EUNSUPPORTED;
   const pdr::MomentWindows mw{win0_col0, win0_cols, win1_cols > 0 ? win1_col0 : win0_col0 + win0_cols,
                               win1_cols > 0 ? win1_cols : 0};
-  // lanes per row from the FULL width, as gather_add_impl: what keeps the order of every column's sum
+  // lanes per row from the FULL width, whatever is walked: what keeps the order of every column's sum
   const int lpr = Cout <= 64 ? 16 : (Cout <= 128 ? 32 : 64);
+  // column passes per workgroup: all of them, unless the launch has fewer tiles than the chip holds workgroups
   const int w4 = (mw.na + 3) / 4 + (mw.nb + 3) / 4;
   const int passes = (w4 + lpr - 1) / lpr;
   const int ncb = (nblocks <= 1024 && passes > 1) ? passes : 1;
   const dim3 grid(static_cast<unsigned>(nblocks), static_cast<unsigned>(ncb));
   hipStream_t st = pdr::as_stream(stream);
-#define PDR_GM_E(LPR, KP, HS, HE)                                                                                     \
-  hipLaunchKernelGGL((gather_moments_kernel<LPR, KP, HS, HE>), grid, dim3(256), 0, st, U, ldu, n_src, V, V0, ldv, idx, \
-                     counts, s1, r1, s2, r2, rows_per_batch, K, Cout, partial, relu_col0, mw, tile_valid,             \
-                     partial_tpb, tw)
-#define PDR_GM_K(LPR, KP, HS)                 \
+#define PDR_G_Y(LPR, KP, HS, HE, YW)                                                                                  \
+  hipLaunchKernelGGL((gather_kernel<LPR, KP, HS, HE, YW>), grid, dim3(256), 0, st, U, ldu, n_src, V, V0, ldv, idx,    \
+                     counts, s1, r1, s2, r2, rows_per_batch, K, Cout, partial, relu_col0, mw, tile_valid, partial_tpb, \
+                     tw, y_window<YW>(Y, ldy, ycol0, ycol0 + y4))
+#define PDR_G_E(LPR, KP, HS, HE)              \
   do {                                        \
-    if (counts) PDR_GM_E(LPR, KP, HS, true);  \
-    else PDR_GM_E(LPR, KP, HS, false);        \
+    if (Y) PDR_G_Y(LPR, KP, HS, HE, true);    \
+    else PDR_G_Y(LPR, KP, HS, HE, false);     \
   } while (0)
-#define PDR_GM(LPR)                                       \
+#define PDR_G_K(LPR, KP, HS)                  \
+  do {                                        \
+    if (counts) PDR_G_E(LPR, KP, HS, true);   \
+    else PDR_G_E(LPR, KP, HS, false);         \
+  } while (0)
+#define PDR_G(LPR)                                        \
   do {                                                    \
-    if (kpow2 && has_s) PDR_GM_K(LPR, true, true);        \
-    else if (kpow2) PDR_GM_K(LPR, true, false);           \
-    else if (has_s) PDR_GM_K(LPR, false, true);           \
-    else PDR_GM_K(LPR, false, false);                     \
+    if (kpow2 && has_s) PDR_G_K(LPR, true, true);         \
+    else if (kpow2) PDR_G_K(LPR, true, false);            \
+    else if (has_s) PDR_G_K(LPR, false, true);            \
+    else PDR_G_K(LPR, false, false);                      \
   } while (0)
-  if (lpr == 16) PDR_GM(16);
-  else if (lpr == 32) PDR_GM(32);
-  else PDR_GM(64);
-#undef PDR_GM
-#undef PDR_GM_K
-#undef PDR_GM_E
+  if (lpr == 16) PDR_G(16);
+  else if (lpr == 32) PDR_G(32);
+  else PDR_G(64);
+#undef PDR_G
+#undef PDR_G_K
+#undef PDR_G_E
+#undef PDR_G_Y
   return pdr::check_launch();
 }
 
@@ -932,8 +779,8 @@ extern "C" int pdr_gather_moments(const float* U, int ldu, int n_src, const floa
                                   const float* r2, int B, int rows_per_batch, int K, int Cout, float* partial,
                                   int relu_col0, int win0_col0, int win0_cols, int win1_col0, int win1_cols,
                                   pdr_stream_t stream) {
-  return gather_moments_impl(U, ldu, n_src, V, V0, ldv, idx, counts, s1, r1, s2, r2, B, rows_per_batch, K, Cout, partial,
-                             relu_col0, win0_col0, win0_cols, win1_col0, win1_cols, nullptr, 0, stream);
+  return gather_launch(U, ldu, n_src, V, V0, ldv, idx, counts, s1, r1, s2, r2, B, rows_per_batch, K, Cout, nullptr, 0,
+                       partial, relu_col0, 0, -1, win0_col0, win0_cols, win1_col0, win1_cols, nullptr, 0, stream);
 }
 
 extern "C" int pdr_gather_moments_tiles(const float* U, int ldu, int n_src, const float* V, const float* V0, int ldv,
@@ -943,8 +790,9 @@ extern "C" int pdr_gather_moments_tiles(const float* U, int ldu, int n_src, cons
                                         int win1_cols, const unsigned char* tile_valid, int partial_tpb,
                                         pdr_stream_t stream) {
   if (!tile_valid || partial_tpb < (rows_per_batch + 127) / 128) return PDR_EINVAL;
-  return gather_moments_impl(U, ldu, n_src, V, V0, ldv, idx, counts, s1, r1, s2, r2, B, rows_per_batch, K, Cout, partial,
-                             relu_col0, win0_col0, win0_cols, win1_col0, win1_cols, tile_valid, partial_tpb, stream);
+  return gather_launch(U, ldu, n_src, V, V0, ldv, idx, counts, s1, r1, s2, r2, B, rows_per_batch, K, Cout, nullptr, 0,
+                       partial, relu_col0, 0, -1, win0_col0, win0_cols, win1_col0, win1_cols, tile_valid, partial_tpb,
+                       stream);
 }
 
 extern "C" int pdr_gather_moments_tiles_twin(const float* U, int ldu, int n_src, const float* V, const float* V0,
@@ -954,9 +802,9 @@ extern "C" int pdr_gather_moments_tiles_twin(const float* U, int ldu, int n_src,
                                              const unsigned char* tile_valid, int partial_tpb, const int* idx0,
                                              float* Yd, int ldyd, const int* wrow0, float wmul, pdr_stream_t stream) {
   if (!tile_valid || !idx0 || rows_per_batch <= 0 || K <= 0 || rows_per_batch % K != 0) return PDR_EINVAL;
-  return gather_moments_impl(U, ldu, n_src, V, V0, ldv, idx, counts, nullptr, nullptr, nullptr, nullptr, B,
-                             rows_per_batch, K, Cout, partial, relu_col0, win0_col0, win0_cols, win1_col0, win1_cols,
-                             tile_valid, partial_tpb, stream, idx0, Yd, ldyd, wrow0, wmul);
+  return gather_launch(U, ldu, n_src, V, V0, ldv, idx, counts, nullptr, nullptr, nullptr, nullptr, B, rows_per_batch, K,
+                       Cout, nullptr, 0, partial, relu_col0, 0, -1, win0_col0, win0_cols, win1_col0, win1_cols, tile_valid,
+                       partial_tpb, stream, idx0, Yd, ldyd, wrow0, wmul);
 }
 
 extern "C" int pdr_gather_add(const float* U, int ldu, int n_src, const float* V, const float* V0,
@@ -964,8 +812,8 @@ extern "C" int pdr_gather_add(const float* U, int ldu, int n_src, const float* V
                               const float* r1, const float* s2, const float* r2, int B,
                               int rows_per_batch, int K, int Cout, float* Y, int ldy, float* partial,
                               int relu_col0, int ycol0, int ycols, pdr_stream_t stream) {
-  return gather_add_impl(U, ldu, n_src, V, V0, ldv, idx, counts, s1, r1, s2, r2, B, rows_per_batch, K, Cout, Y, ldy,
-                         partial, relu_col0, ycol0, ycols, nullptr, 0, stream);
+  return gather_launch(U, ldu, n_src, V, V0, ldv, idx, counts, s1, r1, s2, r2, B, rows_per_batch, K, Cout, Y, ldy, partial,
+                       relu_col0, ycol0, ycols, 0, Cout, 0, 0, nullptr, 0, stream);
 }
 
 // pdr_gather_add over a SUBSET of its 128-row tiles: tile_valid (B * ceil(rows_per_batch / 128)) bytes from
@@ -978,8 +826,8 @@ extern "C" int pdr_gather_add_tiles(const float* U, int ldu, int n_src, const fl
                                     int relu_col0, int ycol0, int ycols, const unsigned char* tile_valid,
                                     int partial_tpb, pdr_stream_t stream) {
   if (!tile_valid || partial_tpb < (rows_per_batch + 127) / 128) return PDR_EINVAL;
-  return gather_add_impl(U, ldu, n_src, V, V0, ldv, idx, counts, s1, r1, s2, r2, B, rows_per_batch, K, Cout, Y, ldy,
-                         partial, relu_col0, ycol0, ycols, tile_valid, partial_tpb, stream);
+  return gather_launch(U, ldu, n_src, V, V0, ldv, idx, counts, s1, r1, s2, r2, B, rows_per_batch, K, Cout, Y, ldy, partial,
+                       relu_col0, ycol0, ycols, 0, Cout, 0, 0, tile_valid, partial_tpb, stream);
 }
 
 // pdr_gather_add_tiles + the block's per-QUERY rows in the same launch (round 5: was a second, K = 1 pdr_gather_add on
@@ -992,7 +840,7 @@ extern "C" int pdr_gather_add_tiles_twin(const float* U, int ldu, int n_src, con
                                          int ycols, const unsigned char* tile_valid, int partial_tpb, const int* idx0,
                                          float* Yd, int ldyd, const int* wrow0, float wmul, pdr_stream_t stream) {
   if (!tile_valid || !idx0 || rows_per_batch <= 0 || K <= 0 || rows_per_batch % K != 0) return PDR_EINVAL;
-  return gather_add_impl(U, ldu, n_src, V, V0, ldv, idx, counts, nullptr, nullptr, nullptr, nullptr, B, rows_per_batch,
-                         K, Cout, Y, ldy, partial, relu_col0, ycol0, ycols, tile_valid, partial_tpb, stream, idx0, Yd,
-                         ldyd, wrow0, wmul);
+  return gather_launch(U, ldu, n_src, V, V0, ldv, idx, counts, nullptr, nullptr, nullptr, nullptr, B, rows_per_batch, K,
+                       Cout, Y, ldy, partial, relu_col0, ycol0, ycols, 0, Cout, 0, 0, tile_valid, partial_tpb, stream, idx0,
+                       Yd, ldyd, wrow0, wmul);
 }

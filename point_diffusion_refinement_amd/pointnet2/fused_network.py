@@ -1503,98 +1503,70 @@ class SplitFirstConv:
         partial = torch.empty((B * ptpb, self.Cout, 2), dtype=torch.float32, device=U.device)
         cptr = counts.data_ptr() if has_v0 else None
 
-        def gather_moments():
-            """The statistics-only pass over `windows` -> (done, Yd); done False: not carried, use gather_add."""
-            w0, w1 = windows[0], (windows[1] if len(windows) > 1 else (0, 0))
-            tabs = (U.data_ptr(), ld, n, V2.data_ptr(), _ptr(V2, ld) if has_v0 else None, ldv, idx32.data_ptr(), cptr)
-            knn = (s1.data_ptr() if s1 is not None else None, self.r1.data_ptr() if s1 is not None else None,
-                   s2.data_ptr() if s2 is not None else None, self.r2.data_ptr() if s2 is not None else None)
-            tail = (partial.data_ptr(), relu_col0, w0[0], w0[1], w1[0], w1[1])
-            if dd is None:
-                rc = lib.pdr_gather_moments(*tabs, *knn, B, rpb, K, self.Cout, *tail, _stream())
-                if rc == _lib.PDR_EUNSUPPORTED:
-                    return False, None
-                _lib.check(rc, "gather_moments")
-                return True, None
-            Yd = torch.empty((B * m, ld), dtype=torch.float32, device=U.device)
-            if TWIN_STATS:
-                rc = lib.pdr_gather_moments_tiles_twin(
-                    *tabs, B, rpb, K, self.Cout, *tail, dd.tile_valid.data_ptr(), ptpb, dd.idx0.data_ptr(),
-                    Yd.data_ptr(), ld, dd.wrow0.data_ptr(), float(K), _stream())
-                if rc == _lib.PDR_EUNSUPPORTED:
-                    return False, None
-                _lib.check(rc, "gather_moments_tiles_twin")
-                sub[0] = (dd.nvalid[0], dd.tpb)
-                return True, Yd
-            rc = lib.pdr_gather_moments_tiles(*tabs, *knn, B, rpb, K, self.Cout, *tail, dd.tile_valid.data_ptr(), ptpb,
-                                              _stream())
-            if rc == _lib.PDR_EUNSUPPORTED:
-                return False, None
-            _lib.check(rc, "gather_moments_tiles")
-            _lib.check(lib.pdr_gather_add(*tabs[:6], dd.idx0.data_ptr(), cptr, None, None, None, None, B, m, 1,
-                                          self.Cout, Yd.data_ptr(), ld, None, relu_col0, 0, -1, _stream()), "gather_add")
-            dd.moments(Yd, self.Cout, relu_col0, partial)
-            return True, Yd
+        # the argument groups every gather entry point shares: the tables, the kNN terms, the shape
+        tabs = (U.data_ptr(), ld, n, V2.data_ptr(), _ptr(V2, ld) if has_v0 else None, ldv)
+        knn = (s1.data_ptr() if s1 is not None else None, self.r1.data_ptr() if s1 is not None else None,
+               s2.data_ptr() if s2 is not None else None, self.r2.data_ptr() if s2 is not None else None)
+        dims = (B, rpb, K, self.Cout)
 
-        def gather_add(y, ldy, ycol0, ycols):
+        def gather(y, ldy, ycol0, ycols):
+            """One pass over the block's rows: the moments of `windows` alone when nothing is written (MOMENT_WINDOWS),
+            else -- or where the windows are not carried -- of the whole width, with the window [ycol0, + ycols) of the
+            output written to y.  -> Yd, the first conv of every query's FIRST neighbour (B m rows: the per-query
+            chain's input), of a deduplicated block; else None."""
+            forms = [("gather_add", (y, ldy, partial.data_ptr(), relu_col0, ycol0, ycols))]
             if y is None and MOMENT_WINDOWS and windows:
-                done, Yd = gather_moments()
-                if done:
-                    return Yd
-            args = (U.data_ptr(), ld, n, V2.data_ptr(), _ptr(V2, ld) if has_v0 else None, ldv, idx32.data_ptr(), cptr,
-                    s1.data_ptr() if s1 is not None else None, self.r1.data_ptr() if s1 is not None else None,
-                    s2.data_ptr() if s2 is not None else None, self.r2.data_ptr() if s2 is not None else None,
-                    B, rpb, K, self.Cout, y, ldy, partial.data_ptr(), relu_col0, ycol0, ycols)
-            if dd is None:
-                _lib.check(lib.pdr_gather_add(*args, _stream()), "gather_add")
-                return None
-            # the first conv of every query's FIRST neighbour, materialised (B m rows): the per-query chain's input
-            Yd = torch.empty((B * m, ld), dtype=torch.float32, device=U.device)
-            if TWIN_STATS:
-                # ... written, with its weighted moments, by extra workgroups of the launch that walks the tile subset
-                _lib.check(lib.pdr_gather_add_tiles_twin(
-                    U.data_ptr(), ld, n, V2.data_ptr(), _ptr(V2, ld) if has_v0 else None, ldv, idx32.data_ptr(), cptr,
-                    B, rpb, K, self.Cout, y, ldy, partial.data_ptr(), relu_col0, ycol0, ycols,
-                    dd.tile_valid.data_ptr(), ptpb, dd.idx0.data_ptr(), Yd.data_ptr(), ld, dd.wrow0.data_ptr(),
-                    float(K), _stream()), "gather_add_tiles_twin")
+                w0, w1 = windows[0], (windows[1] if len(windows) > 1 else (0, 0))
+                forms.insert(0, ("gather_moments", (partial.data_ptr(), relu_col0, w0[0], w0[1], w1[0], w1[1])))
+            Yd = torch.empty((B * m, ld), dtype=torch.float32, device=U.device) if dd is not None else None
+            for name, out in forms:
+                head = (*tabs, idx32.data_ptr(), cptr)
+                if dd is None:
+                    rc = getattr(lib, "pdr_" + name)(*head, *knn, *dims, *out, _stream())
+                elif TWIN_STATS:
+                    # Yd is written, with its weighted moments, by extra workgroups of the launch that walks the tile subset
+                    name += "_tiles_twin"
+                    rc = getattr(lib, "pdr_" + name)(*head, *dims, *out, dd.tile_valid.data_ptr(), ptpb, dd.idx0.data_ptr(),
+                                                     Yd.data_ptr(), ld, dd.wrow0.data_ptr(), float(K), _stream())
+                else:
+                    name += "_tiles"
+                    rc = getattr(lib, "pdr_" + name)(*head, *knn, *dims, *out, dd.tile_valid.data_ptr(), ptpb, _stream())
+                if rc != _lib.PDR_EUNSUPPORTED:             # (windows off a float4 are not carried: the whole width)
+                    break
+            _lib.check(rc, name)
+            if dd is not None and TWIN_STATS:
                 sub[0] = (dd.nvalid[0], dd.tpb)
-                return Yd
-            _lib.check(lib.pdr_gather_add_tiles(*args, dd.tile_valid.data_ptr(), ptpb, _stream()), "gather_add_tiles")
-            _lib.check(lib.pdr_gather_add(
-                U.data_ptr(), ld, n, V2.data_ptr(), _ptr(V2, ld) if has_v0 else None, ldv, dd.idx0.data_ptr(), cptr,
-                None, None, None, None, B, m, 1, self.Cout, Yd.data_ptr(), ld, None, relu_col0, 0, -1, _stream()),
-                "gather_add")
-            dd.moments(Yd, self.Cout, relu_col0, partial)
+            elif dd is not None:
+                _lib.check(lib.pdr_gather_add(*tabs, dd.idx0.data_ptr(), cptr, None, None, None, None, B, m, 1, self.Cout,
+                                              Yd.data_ptr(), ld, None, relu_col0, 0, -1, _stream()), "gather_add")
+                dd.moments(Yd, self.Cout, relu_col0, partial)
             return Yd
 
         # (a thunk: the fold is launched by whoever consumes it, i.e. on the stream that runs the rest of the MLP)
-        sub = [None]                                   # set by gather_add: the statistics of a tile subset
+        sub = [None]                                   # set by gather: the statistics of a tile subset
         folded = (lambda: fold.launch(Stats(partial, ptpb, sub[0]), B)) if fold is not None else None
 
         if not virtual:
-            gather_add(Y.data_ptr(), ld, 0, -1)
+            gather(Y.data_ptr(), ld, 0, -1)
             return FirstOut(Y=Y, stats=Stats(partial, tpb)), folded
         # virtual: GroupNorm moments of every column, but only the residual columns (a row-wise add in their
         # consumer, which stays a plain read) are written -- one pass
         Yres = None
         if res is not None and res[1] <= GATHER_RES and (s1 is None or GATHER_RES_KNN):
             res = None                        # consumers gather the residual window like any other
-            Yd = gather_add(None, ld, 0, -1)
+            Yd = gather(None, ld, 0, -1)
         elif res is not None and res[0] % 4 == 0:
             Yres = torch.empty((B * rpb, _pad4(res[1])), dtype=torch.float32, device=U.device)
-            Yd = gather_add(Yres.data_ptr(), Yres.shape[1], res[0], res[1])
+            Yd = gather(Yres.data_ptr(), Yres.shape[1], res[0], res[1])
         else:
             res = None
-            Yd = gather_add(None, ld, 0, -1)
+            Yd = gather(None, ld, 0, -1)
         def materialise(col0, C):
             """Columns [col0, col0 + C) of the conv output as a tensor (fallback of consumers that cannot gather)."""
             assert col0 % 4 == 0
             Yc = torch.empty((B * rpb, _pad4(C)), dtype=torch.float32, device=U.device)
-            _lib.check(lib.pdr_gather_add(
-                U.data_ptr(), ld, n, V2.data_ptr(), _ptr(V2, ld) if has_v0 else None, ldv, idx32.data_ptr(), cptr,
-                s1.data_ptr() if s1 is not None else None, self.r1.data_ptr() if s1 is not None else None,
-                s2.data_ptr() if s2 is not None else None, self.r2.data_ptr() if s2 is not None else None,
-                B, rpb, K, self.Cout, Yc.data_ptr(), Yc.shape[1], None, relu_col0, col0, C, _stream()), "gather_add")
+            _lib.check(lib.pdr_gather_add(*tabs, idx32.data_ptr(), cptr, *knn, *dims, Yc.data_ptr(), Yc.shape[1], None,
+                                          relu_col0, col0, C, _stream()), "gather_add")
             return Yc
 
         first = FirstOut(stats=Stats(partial, ptpb, sub[0]), U=U, V2=V2, ld=ld, has_v0=has_v0, idx=idx32,

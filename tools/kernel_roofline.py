@@ -86,18 +86,22 @@ def _work(name, args, lib):
         ws = int(li.rows_per_batch % tm == 0 and vid not in (3, 6))
         byt = 4.0 * P * (Cin + D) + 4.0 * (P // K) * D
         return _layer_symbol((ws, vid, False, 0, 1, 0), pool=True), 2.0 * P * Cin * D, byt
-    if name == "pdr_gather_add":
-        ldu, n_src, B, rpb, K, Cout, Y, ycols = args[1], args[2], args[12], args[13], args[14], args[15], args[16], args[21]
+    if name in ("pdr_gather_add", "pdr_gather_moments"):
+        # ONE kernel body behind both entry points (fused_gather.hip: gather_kernel<LPR, KPOW2, HAS_S, HAS_EM, YWIN>); the
+        # entry point stays in the symbol, so the whole-width and the window passes are groups of their own
+        n_src, counts, s1, s2, B, rpb, K, Cout = args[2], args[7], args[8], args[10], args[12], args[13], args[14], args[15]
         P = B * rpb
-        byt = 4.0 * (B * n_src * Cout + (P // K) * Cout + P) + (4.0 * P * (ycols if ycols > 0 else Cout) if Y else 0.0)
-        lpr = 16 if Cout <= 64 else (32 if Cout <= 128 else 64)
-        return "gather_add_kernel<%d>" % lpr, 2.0 * P * Cout, byt
-    if name == "pdr_gather_moments":
-        # the statistics-only pass over its column windows: table + query rows of those columns + index, nothing written
-        n_src, B, rpb, K, Cout, cols = args[2], args[12], args[13], args[14], args[15], args[19] + max(args[21], 0)
-        P = B * rpb
-        lpr = 16 if Cout <= 64 else (32 if Cout <= 128 else 64)
-        return "gather_moments_kernel<%d>" % lpr, 2.0 * P * cols, 4.0 * (B * n_src * cols + (P // K) * cols + P)
+        if name == "pdr_gather_add":
+            Y, ycols = args[16], args[21]
+            cols, written = Cout, (ycols if ycols > 0 else Cout) if Y else 0
+        else:
+            # the statistics-only pass over its column windows: table + query rows of those columns + index, nothing written
+            Y, cols, written = None, args[19] + max(args[21], 0), 0
+        tf = lambda v: "true" if v else "false"
+        sym = "gather_kernel<%d, %s, %s, %s, %s> (%s)" % (
+            16 if Cout <= 64 else (32 if Cout <= 128 else 64), tf((K & (K - 1)) == 0 and K <= 32), tf(s1 or s2), tf(counts),
+            tf(Y), name)
+        return sym, 2.0 * P * cols, 4.0 * (B * n_src * cols + (P // K) * cols + P) + 4.0 * P * written
     if name == "pdr_attention_pool":
         B, npoint, K, D = args[8], args[9], args[10], args[11]
         P = B * npoint * K
@@ -153,7 +157,7 @@ def measured_traffic(symbol):
     path = latest_traffic_file()
     if path is None:
         raise LookupError("no profiles/r*_pmc_traffic.json")
-    key = symbol.replace(" ", "")
+    key = symbol.split(" (")[0].replace(" ", "")         # (without the entry point behind a gather_kernel symbol)
     stem = key[:-1] if key.endswith(">") else key       # a profile of a build with more (trailing) template arguments
     kernels = json.load(open(path))["kernels"]
     for exact in (True, False):
