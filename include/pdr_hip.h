@@ -61,7 +61,7 @@ typedef void *pdr_stream_t; /* hipStream_t */
  *                (int[16]), pdr_set_option replaces the environment knobs, pdr_point_chain / pdr_point_chain_plan /
  *                pdr_fused_layer_pair are new; pdr_knn_points_ragged / pdr_chamfer_nn_ragged are new; pdr_approxmatch_ragged /
  *                pdr_emd_cost_ragged / pdr_matchcost_ragged / pdr_matchcost_grad_ragged are new; pdr_emd_cost_grad /
- *                pdr_emd_cost_grad_ragged are new. */
+ *                pdr_emd_cost_grad_ragged are new; pdr_chamfer_pairwise is new. */
 int pdr_version(void);
 /* last hip error string seen by this thread after a PDR_ELAUNCH ("" if none) */
 const char *pdr_last_error(void);
@@ -183,6 +183,35 @@ int pdr_chamfer_nn(const float *x, const float *y, int B, int n1, int n2, float 
 int pdr_chamfer_nn_ragged(const float *x, const float *y, const int64_t *lengths1, const int64_t *lengths2,
                           int B, int n1, int n2, float *dist_xy, int64_t *idx_xy, float *dist_yx, int64_t *idx_yx,
                           pdr_stream_t stream);
+/* All-pairs Chamfer distance between two SETS of clouds (the Chamfer half of _pairwise_EMD_CD_,
+ * pointnet2/models/pvd/metrics/evaluation_metrics.py:45-78, which expands one cloud R times, calls chamfer_distance and
+ * reduces 2 (n + m) distances per pair with torch launches):  x (S,n,3), y (R,m,3)  ->  cd (S,R) f32, fully written,
+ *     cd[s,r] = (1/n_s) sum_i min_j |x_s,i - y_r,j|^2  +  (1/m_r) sum_j min_i |x_s,i - y_r,j|^2
+ * = calc_cd's cd_t = the reference's dl.mean(1) + dr.mean(1), one float per pair; nothing per point is stored and no
+ * index is recovered.  ONE launch (a workgroup per pair), no workspace, no atomics, no allocation, no synchronisation:
+ * capturable like every call here.
+ *   - lengths_x / lengths_y follow the rules of pdr_knn_points_ragged: int64 arrays of S / R entries in DEVICE memory,
+ *     read by the kernel only and clamped there to [0, n] / [0, m]; NULL = every cloud is full; n / m stay the row
+ *     strides.  Rows at or beyond a cloud's length are never queries and never candidates, whatever they hold (NaN
+ *     included).  A pair with an empty side gets cd = 0 (what calc_cd gives).  A pair's value depends on its two
+ *     clouds' valid rows only: with NULL or full lengths the result is bit-identical to the call without lengths, and a
+ *     ragged pair gets the bits of the dense call on the two slices.
+ *   - the distance is the knn expression (fma(dz, dz, fma(dy, dy, dx * dx)) on the differences, never the expanded
+ *     |x|^2 + |y|^2 - 2 x.y): every per-point minimum has the bits pdr_chamfer_nn returns for that pair.
+ *   - the sums are deterministic: their order is fixed by the code (per thread in ascending query order, then a fixed
+ *     tree), so the same input gives the same bits run after run.  The longest chain of dependent fp32 roundings is
+ *     ceil(max(n, m) / 256) + 10 -- 74 for n, m <= 16384 --, and every addend is non-negative: cd is within
+ *     74 * 2^-24 relative of the exact sum of the fp32 minima.
+ *   - symmetric != 0 is the self-matrix: it requires x == y, lengths_x == lengths_y, S == R and n == m (PDR_EINVAL
+ *     otherwise, checked before anything else but the signs of the sizes).  Only the pairs s <= r are evaluated and
+ *     their owner writes cd[s,r] and cd[r,s]: roughly half the work.  The matrix is bitwise symmetric, equal bit for
+ *     bit to the plain call on (x, x) (whose two triangles add the same two sums in opposite order), and its diagonal
+ *     is exactly 0 for non-empty clouds of finite points (a point's distance to itself is exactly 0 here).
+ *   - validation: a negative size: PDR_EINVAL; S == 0 or R == 0: PDR_OK, nothing done, no pointer looked at;
+ *     n <= 0 or m <= 0 with S, R > 0: PDR_EINVAL (as pdr_chamfer_nn); NULL x / y / cd: PDR_EINVAL; more than 2^30
+ *     pairs: PDR_EUNSUPPORTED.  cd and the clouds are indexed in size_t. */
+int pdr_chamfer_pairwise(const float *x, const float *y, const int64_t *lengths_x, const int64_t *lengths_y,
+                         int S, int R, int n, int m, int symmetric, float *cd, pdr_stream_t stream);
 /* pdr_knn_points for group_knn (pointnet2_utils.py:487-514) inside the fused network: same search, int32 indices
  * and the normalised interpolation weights w = (1/(d2+1e-8)) / sum_k (1/(d2_k+1e-8)) of :500-503 (SQUARED
  * distances, k ascending) in the same pass.  Requires K <= min(n2, 16). */

@@ -118,15 +118,24 @@ def matchcost_backward(grad_cost, xyz1, xyz2, match, lengths1=None, lengths2=Non
     return [g1, g2]
 
 
-def emd_cost_fused(xyz1, xyz2, lengths1=None, lengths2=None, return_workspace=False):
+def emd_cost_fused(xyz1, xyz2, lengths1=None, lengths2=None, return_workspace=False, workspace=None):
     """matchcost(approxmatch(xyz1, xyz2)) without the match matrix (no autograd).  return_workspace: -> (cost, temp),
-    temp the call's workspace holding the per-level factors emd_cost_backward reads (layout private)."""
+    temp the call's workspace holding the per-level factors emd_cost_backward reads (layout private).  workspace: a
+    float32 tensor of at least pdr_emd_workspace_bytes(B, n, m) bytes to use instead of allocating one (a caller that
+    walks many batches, set_metrics.pairwise_emd, allocates it once)."""
     _check(xyz1, "xyz1"), _check(xyz2, "xyz2")
     B, n, _ = xyz1.shape
     m = xyz2.shape[1]
     lib = _lib.load()
     cost = torch.empty((B,), dtype=torch.float32, device=xyz1.device)
-    temp = torch.empty((lib.pdr_emd_workspace_bytes(B, n, m) // 4,), dtype=torch.float32, device=xyz1.device)
+    if workspace is None:
+        temp = torch.empty((lib.pdr_emd_workspace_bytes(B, n, m) // 4,), dtype=torch.float32, device=xyz1.device)
+    else:
+        temp = workspace
+        if (temp.dtype != torch.float32 or temp.device != xyz1.device or not temp.is_contiguous()
+                or temp.numel() * 4 < lib.pdr_emd_workspace_bytes(B, n, m)):
+            raise RuntimeError("workspace must be a contiguous float32 tensor on the clouds' device of at least "
+                               "pdr_emd_workspace_bytes(B, n, m) bytes")
     with torch.cuda.device(xyz1.device):
         if lengths1 is None and lengths2 is None:
             _lib.check(lib.pdr_emd_cost(xyz1.data_ptr(), xyz2.data_ptr(), B, n, m, cost.data_ptr(), temp.data_ptr(),

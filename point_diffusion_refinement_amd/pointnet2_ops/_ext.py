@@ -243,6 +243,29 @@ def chamfer_nn(x, y, x_lengths=None, y_lengths=None):
     return dx, ix, dy, iy
 
 
+def chamfer_pairwise(x, y, x_lengths=None, y_lengths=None, symmetric=False):
+    """All-pairs Chamfer distance between two sets of clouds in one launch (pdr_chamfer_pairwise):
+    (S,n,3), (R,m,3) -> cd (S,R) f32, cd[s,r] = mean_i min_j |x_s,i - y_r,j|^2 + mean_j min_i (the same); not
+    differentiable.  `x_lengths` (S,) / `y_lengths` (R,) int64 on the clouds' device: cloud s is x[s, :x_lengths[s]];
+    a pair with an empty side gets 0.  symmetric=True is the self-matrix: `y` must be `x` and `y_lengths` `x_lengths`
+    (same memory); only the pairs s <= r are evaluated and mirrored."""
+    _req(x, "x", torch.float32)
+    _req(y, "y", torch.float32)
+    _same_device(x, y)
+    _req_xyz(x, "x")
+    _req_xyz(y, "y")
+    _req_lengths(x_lengths, "x_lengths", x)
+    _req_lengths(y_lengths, "y_lengths", y)
+    S, n, _ = x.shape
+    R, m, _ = y.shape
+    cd = torch.empty((S, R), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.load().pdr_chamfer_pairwise(x.data_ptr(), y.data_ptr(), _ptr(x_lengths), _ptr(y_lengths), S, R,
+                                                    n, m, 1 if symmetric else 0, cd.data_ptr(), _stream()),
+                   "chamfer_pairwise")
+    return cd
+
+
 def knn_group(x, y, K):
     """knn_points for group_knn in the fused network: (dists (B,n1,K) f32, idx (B,n1,K) i32, weights (B,n1,K) f32)
     with weights = normalised 1 / (d2 + 1e-8) (pointnet2_utils.py:500-503)."""
