@@ -61,7 +61,8 @@ typedef void *pdr_stream_t; /* hipStream_t */
  *                (int[16]), pdr_set_option replaces the environment knobs, pdr_point_chain / pdr_point_chain_plan /
  *                pdr_fused_layer_pair are new; pdr_knn_points_ragged / pdr_chamfer_nn_ragged are new; pdr_approxmatch_ragged /
  *                pdr_emd_cost_ragged / pdr_matchcost_ragged / pdr_matchcost_grad_ragged are new; pdr_emd_cost_grad /
- *                pdr_emd_cost_grad_ragged are new; pdr_chamfer_pairwise is new. */
+ *                pdr_emd_cost_grad_ragged are new; pdr_chamfer_pairwise is new; pdr_fps_plan / pdr_knn_plan /
+ *                pdr_ball_query_plan (host-only dispatch queries) are new. */
 int pdr_version(void);
 /* last hip error string seen by this thread after a PDR_ELAUNCH ("" if none) */
 const char *pdr_last_error(void);
@@ -102,6 +103,11 @@ int pdr_opt_n_threads(int work_size);
 size_t pdr_fps_workspace_bytes(int B, int N);
 int pdr_furthest_point_sampling(const float *xyz, int B, int N, int m,
                                 float *temp, int *idx, pdr_stream_t stream);
+/* Which kernel pdr_furthest_point_sampling runs for a cloud of N points under the current fps_wave / fps_lean options.
+ * Host only (no HIP call, no device pointer); the launch reads the same decision, so the kernel that runs is the one
+ * reported.  out = {family (0 resident, 1 wave, 2 lean, 3 stream), threads per cloud T, points per thread PPT (0: the
+ * stream kernel strides), slots = R Q with R = pdr_opt_n_threads(N), Q = ceil(N / R)}.  N <= 0: PDR_EINVAL. */
+int pdr_fps_plan(int N, int out[4]);
 
 /* ---- gather -----------------------------------------------------------------
  * gather_points(points (B,C,N), idx (B,m)) -> out (B,C,m)   sampling.cpp:15-38
@@ -119,6 +125,11 @@ int pdr_gather_points_grad(const float *grad_out, const int *idx, int B, int C,
 int pdr_ball_query(const float *new_xyz, const float *xyz, int B, int n, int m,
                    float radius, int nsample, int *idx, int *counts,
                    pdr_stream_t stream);
+/* Which instantiation pdr_ball_query runs for these sizes (host only, read by the launch itself):
+ * out = {NCH (64-point cloud slots per lane), resident (1: n <= 64 NCH, the cloud lives in registers; 0: the streaming
+ * kernel), queries per wave, workgroups per cloud}; all 0 for an empty call (B == 0 or m == 0), which launches nothing.
+ * B < 0, n <= 0 or m < 0: PDR_EINVAL, as the call. */
+int pdr_ball_query_plan(int B, int n, int m, int out[4]);
 
 /* ---- grouping ---------------------------------------------------------------
  * group_points(points (B,C,N), idx (B,np,ns)) -> out (B,C,np,ns)
@@ -217,6 +228,14 @@ int pdr_chamfer_pairwise(const float *x, const float *y, const int64_t *lengths_
  * distances, k ascending) in the same pass.  Requires K <= min(n2, 16). */
 int pdr_knn_group(const float *x, const float *y, int B, int n1, int n2, int K, float *dists, int *idx,
                   float *weights, pdr_stream_t stream);
+/* Which kernel pdr_knn_points / pdr_knn_points_ragged (group = 0; has_nn != 0: `nn` is asked for) or pdr_knn_group
+ * (group = 1) runs for these sizes under the current knn_wave option.  Host only; the launches read the same decision.
+ * out = {family (0 thread per query, 1 wave per query, 2 packed K = 1; -1: an empty call, nothing is launched), the
+ * kernel's template parameter (thread: KMAX 1 / 4 / 8 / 16 / 32; wave: NCH 1 / 2 / 4 / 8 / 16 cloud slots per lane;
+ * packed: query pairs per thread), queries per wave (0 outside the wave kernel), workgroups per cloud}.
+ * Returns what the call itself returns before it looks at a pointer: PDR_EINVAL for a negative size or K <= 0 (group:
+ * also n2 <= 0 or K > n2), PDR_EUNSUPPORTED for K > 32 (group: K > 16). */
+int pdr_knn_plan(int B, int n1, int n2, int K, int has_nn, int group, int out[4]);
 
 /* Backward of pdr_knn_points w.r.t. both clouds (pytorch3d knn_points backward, norm 2;
  * makes chamfer_loss_new.py:149-167 / calc_cd :234-245 differentiable as train.py:518 needs;

@@ -26,9 +26,11 @@ SIGNATURES = {
     "pdr_opt_n_threads": (_I, [_I]),
     "pdr_fps_workspace_bytes": (_Z, [_I, _I]),
     "pdr_furthest_point_sampling": (_I, [_P, _I, _I, _I, _P, _P, _P]),
+    "pdr_fps_plan": (_I, [_I, _P]),
     "pdr_gather_points": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),
     "pdr_gather_points_grad": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),
     "pdr_ball_query": (_I, [_P, _P, _I, _I, _I, _F, _I, _P, _P, _P]),
+    "pdr_ball_query_plan": (_I, [_I, _I, _I, _P]),
     "pdr_group_points": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P]),
     "pdr_group_points_grad": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P]),
     "pdr_three_nn": (_I, [_P, _P, _I, _I, _I, _P, _P, _P]),
@@ -40,6 +42,7 @@ SIGNATURES = {
     "pdr_chamfer_nn_ragged": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P]),
     "pdr_chamfer_pairwise": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P]),
     "pdr_knn_group": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
+    "pdr_knn_plan": (_I, [_I, _I, _I, _I, _I, _I, _P]),
     "pdr_knn_points_grad": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
     "pdr_emd_workspace_bytes": (_Z, [_I, _I, _I]),
     "pdr_matchcost_workspace_bytes": (_Z, [_I, _I, _I]),

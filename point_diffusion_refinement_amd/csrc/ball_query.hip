@@ -124,40 +124,80 @@ __global__ __launch_bounds__(256) void ball_query_kernel(
   }
 }
 
-template <int NCH, bool RESIDENT>
-int launch(const float* new_xyz, const float* xyz, int B, int n, int m, float radius2,
-           int nsample, int* idx, int* counts, hipStream_t s) {
+// ---- the dispatch decision: ONE host function, read by pdr_ball_query and pdr_ball_query_plan -----------------------
+struct BallPlan {
+  int nch;        // cloud slots per lane of the instantiation (the streaming kernel is instantiated with 1)
+  int resident;   // 1: the cloud lives in VGPRs (n <= 64 nch); 0: the streaming kernel
+  int qpw;        // queries per wave
+  int gx;         // workgroups per cloud (grid.x)
+};
+
+int plan_ball_query(int B, int n, int m, BallPlan* p) {
+  if (B < 0 || n <= 0 || m < 0) return PDR_EINVAL;
+  p->nch = p->resident = p->qpw = p->gx = 0;
+  if (B == 0 || m == 0) return PDR_OK;   // nothing is launched
+  constexpr int kResident[] = {1, 2, 4, 8, 16, 32, 48, 64};
+  p->nch = 1;
+  for (const int nch : kResident)
+    if (n <= 64 * nch) {
+      p->nch = nch, p->resident = 1;
+      break;
+    }
   // queries per wave: amortise the register fill of the cloud (n*12 B per wave)
   // while keeping >= ~2 workgroups per CU for B*m large enough.
   int qpw = 16;
   while (qpw > 1 && static_cast<long long>(B) * ((m + 4 * qpw - 1) / (4 * qpw)) < 1024) qpw >>= 1;
-  dim3 grid((m + 4 * qpw - 1) / (4 * qpw), B);
-  hipLaunchKernelGGL((ball_query_kernel<NCH, RESIDENT>), grid, dim3(256), 0, s, new_xyz, xyz, n,
-                     m, radius2, nsample, qpw, idx, counts);
+  p->qpw = qpw;
+  p->gx = (m + 4 * qpw - 1) / (4 * qpw);
+  return PDR_OK;
+}
+
+template <int NCH, bool RESIDENT>
+int launch(const BallPlan& p, const float* new_xyz, const float* xyz, int B, int n, int m, float radius2,
+           int nsample, int* idx, int* counts, hipStream_t s) {
+  hipLaunchKernelGGL((ball_query_kernel<NCH, RESIDENT>), dim3(p.gx, B), dim3(256), 0, s, new_xyz, xyz, n,
+                     m, radius2, nsample, p.qpw, idx, counts);
   return pdr::check_launch();
 }
 
 }  // namespace
 
+// Which instantiation pdr_ball_query runs for these sizes (host only): out = {NCH, resident (1 / 0: the streaming
+// kernel), queries per wave, workgroups per cloud}; all 0 for an empty call, which launches nothing.
+extern "C" int pdr_ball_query_plan(int B, int n, int m, int out[4]) {
+  if (!out) return PDR_EINVAL;
+  BallPlan p;
+  const int rc = plan_ball_query(B, n, m, &p);
+  if (rc != PDR_OK) return rc;
+  out[0] = p.nch, out[1] = p.resident, out[2] = p.qpw, out[3] = p.gx;
+  return PDR_OK;
+}
+
 extern "C" int pdr_ball_query(const float* new_xyz, const float* xyz, int B, int n, int m,
                               float radius, int nsample, int* idx, int* counts,
                               pdr_stream_t stream) {
-  if (B < 0 || n <= 0 || m < 0 || nsample <= 0) return PDR_EINVAL;
+  BallPlan p;
+  const int rc = plan_ball_query(B, n, m, &p);
+  if (rc != PDR_OK) return rc;
+  if (nsample <= 0) return PDR_EINVAL;
   if (B == 0 || m == 0) return PDR_OK;
   if (!new_xyz || !xyz || !idx || !counts) return PDR_EINVAL;
   hipStream_t s = pdr::as_stream(stream);
   const float radius2 = radius * radius;  // f32, as ball_query_gpu.cu:24
+  if (!p.resident) return launch<1, false>(p, new_xyz, xyz, B, n, m, radius2, nsample, idx, counts, s);
 #define PDR_BQ_CASE(NCH) \
-  if (n <= 64 * (NCH))   \
-  return launch<NCH, true>(new_xyz, xyz, B, n, m, radius2, nsample, idx, counts, s)
-  PDR_BQ_CASE(1);
-  PDR_BQ_CASE(2);
-  PDR_BQ_CASE(4);
-  PDR_BQ_CASE(8);
-  PDR_BQ_CASE(16);
-  PDR_BQ_CASE(32);
-  PDR_BQ_CASE(48);
-  PDR_BQ_CASE(64);
+  case NCH:              \
+    return launch<NCH, true>(p, new_xyz, xyz, B, n, m, radius2, nsample, idx, counts, s)
+  switch (p.nch) {
+    PDR_BQ_CASE(1);
+    PDR_BQ_CASE(2);
+    PDR_BQ_CASE(4);
+    PDR_BQ_CASE(8);
+    PDR_BQ_CASE(16);
+    PDR_BQ_CASE(32);
+    PDR_BQ_CASE(48);
+    PDR_BQ_CASE(64);
+  }
 #undef PDR_BQ_CASE
-  return launch<1, false>(new_xyz, xyz, B, n, m, radius2, nsample, idx, counts, s);
+  return PDR_EUNSUPPORTED;
 }

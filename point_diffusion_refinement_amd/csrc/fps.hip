@@ -582,73 +582,124 @@ extern "C" size_t pdr_fps_workspace_bytes(int B, int N) {
   return (N <= 12288) ? 0 : static_cast<size_t>(B) * N * sizeof(float);
 }
 
+namespace {
+
+// ---- the dispatch decision: ONE host function, read by the launch below and by pdr_fps_plan ------------------------
+enum FpsFamily { kFpsResident = 0, kFpsWave = 1, kFpsLean = 2, kFpsStream = 3 };
+
+struct FpsPlan {
+  int family, T, PPT;     // kernel family and its template parameters (stream: 1024 threads, PPT 0 = strided)
+  int R, Rbits, Q;        // the reference's thread geometry: R = opt_n_threads(N), Q = ceil(N / R); tie rank < R Q
+};
+
+// Measured on MI355X, B = 32 (tools/lab/fps_time.py), us per call:
+//                      2048->1024  1024->256  256->64  3072->1024
+//   4 waves, barrier        490        105       25        566      (fps_resident_kernel, default above 256 slots)
+//   1 wave, 32 slots/lane   696        121       20         --      (one wave issues <= 1 instruction / ~4-5 cycles)
+//   4 waves, rank-ordered   532        127       20        665      (fewer VALU slots, but the round is a LATENCY
+//                                                                    chain: LDS read -> update -> tree -> 2 DPP
+//                                                                    reductions -> exchange -> index recovery)
+// so the rank-ordered variant (fps_wave_kernel) is used where it wins (<= 256 slots: no barrier at all).  Option
+// fps_wave: 0 = never, 2 = for every size up to 4096 slots (A/B and test runs).
+int plan_fps(int N, FpsPlan* p) {
+  if (N <= 0) return PDR_EINVAL;
+  p->R = pdr_opt_n_threads(N);
+  p->Rbits = 0;
+  while ((1 << p->Rbits) < p->R) ++p->Rbits;
+  p->Q = (N + p->R - 1) / p->R;
+  const auto pick = [p](int family, int T, int PPT) {
+    p->family = family, p->T = T, p->PPT = PPT;
+    return PDR_OK;
+  };
+  if (pdr_fps_workspace_bytes(1, N) > 0) return pick(kFpsStream, 1024, 0);
+  const long slots = static_cast<long>(p->R) * p->Q;
+  const int wave_mode = pdr::option(pdr::OPT_FPS_WAVE);
+  const bool use_wave = wave_mode == 2 || (wave_mode == 1 && slots <= 256);
+  // the wave and lean kernels keep the cloud in N * 16 bytes of dynamic LDS next to their static exchange slots: stay
+  // inside the 64 KiB a launch gets without raising hipFuncAttributeMaxDynamicSharedMemorySize, else the resident kernel
+  const bool fits64k = static_cast<size_t>(N) * sizeof(float4) + 256 <= 64 * 1024;
+  if (use_wave && fits64k && slots <= 4096) {
+    // rank-ordered slots + packed distances + tree arg-max (fps_wave_kernel): ONE wave while a lane holds <= 4
+    // slots (no barrier at all), four waves (one per SIMD: a single wave issues at most one instruction every
+    // ~4-5 cycles, measured 680 ns per round with 32 slots per lane) above that
+    if (slots <= 128) return pick(kFpsWave, 64, 2);
+    if (slots <= 256) return pick(kFpsWave, 64, 4);
+    if (slots <= 512) return pick(kFpsWave, 256, 2);
+    if (slots <= 1024) return pick(kFpsWave, 256, 4);
+    if (slots <= 2048) return pick(kFpsWave, 256, 8);
+    return pick(kFpsWave, 256, 16);
+  }
+  // instruction-lean resident kernel (fps_lean_kernel): clouds whose float4 image fits the 64 KiB, an even number of
+  // points per thread.  Option fps_lean = 0: the round-1 resident kernel.
+  if (pdr::option(pdr::OPT_FPS_LEAN) != 0 && N > 128 && fits64k) {
+    if (N <= 512) return pick(kFpsLean, 256, 2);
+    if (N <= 1024) return pick(kFpsLean, 256, 4);
+    if (N <= 2048) return pick(kFpsLean, 256, 8);
+    if (N <= 3072) return pick(kFpsLean, 256, 12);
+    return pick(kFpsLean, 256, 16);
+  }
+  static_assert(kMaxResidentN >= 12288, "resident path must cover the LDS-resident range");
+  // (512 / 1024 threads per cloud -- fewer points per thread against a wider exchange --, round 5, us per call at B = 32:
+  // 2048->1024 492 / 525 / 885, 1024->256 105 / 124 / 215 for 256 / 512 / 1024 threads: not taken)
+  constexpr int kResident[][2] = {{64, 1},   {64, 2},   {256, 1},   {256, 2},  {256, 4},
+                                  {256, 8},  {256, 12}, {256, 16},  {1024, 8}, {1024, 12}};
+  for (const auto& c : kResident)
+    if (N <= c[0] * c[1]) return pick(kFpsResident, c[0], c[1]);
+  return PDR_EUNSUPPORTED;
+}
+
+}  // namespace
+
+// Which kernel pdr_furthest_point_sampling runs for a cloud of N points under the current fps_wave / fps_lean options
+// (host only): out = {family (0 resident, 1 wave, 2 lean, 3 stream), T, PPT, slots = R Q}.
+extern "C" int pdr_fps_plan(int N, int out[4]) {
+  if (!out) return PDR_EINVAL;
+  FpsPlan p;
+  const int rc = plan_fps(N, &p);
+  if (rc != PDR_OK) return rc;
+  out[0] = p.family, out[1] = p.T, out[2] = p.PPT, out[3] = p.R * p.Q;
+  return PDR_OK;
+}
+
 extern "C" int pdr_furthest_point_sampling(const float* xyz, int B, int N, int m,
                                            float* temp, int* idx, pdr_stream_t stream) {
   if (B < 0 || N <= 0 || m < 0) return PDR_EINVAL;
   if (B == 0 || m == 0) return PDR_OK;
   if (!xyz || !idx) return PDR_EINVAL;
   hipStream_t s = pdr::as_stream(stream);
-  const int R = pdr_opt_n_threads(N);
-  int Rbits = 0;
-  while ((1 << Rbits) < R) ++Rbits;
-  const int Q = (N + R - 1) / R;
-  if (pdr_fps_workspace_bytes(B, N) > 0) {
+  FpsPlan p;
+  const int rc = plan_fps(N, &p);
+  if (rc != PDR_OK) return rc;
+  if (p.family == kFpsStream) {
     if (!temp) return PDR_EINVAL;
-    hipLaunchKernelGGL(fps_stream_kernel, dim3(B), dim3(1024), 0, s, xyz, N, m, R, Rbits, Q,
-                       temp, idx);
+    hipLaunchKernelGGL(fps_stream_kernel, dim3(B), dim3(1024), 0, s, xyz, N, m, p.R, p.Rbits, p.Q, temp, idx);
     return pdr::check_launch();
   }
-  // Rank-ordered variant (fps_wave_kernel).  Measured on MI355X, B = 32 (tools/lab/fps_time.py), us per call:
-  //                      2048->1024  1024->256  256->64  3072->1024
-  //   4 waves, barrier        490        105       25        566      (fps_resident_kernel, default above 256 slots)
-  //   1 wave, 32 slots/lane   696        121       20         --      (one wave issues <= 1 instruction / ~4-5 cycles)
-  //   4 waves, rank-ordered   532        127       20        665      (fewer VALU slots, but the round is a LATENCY
-  //                                                                    chain: LDS read -> update -> tree -> 2 DPP
-  //                                                                    reductions -> exchange -> index recovery)
-  // so it is used where it wins (<= 256 slots: no barrier at all).  Option fps_wave:
-  // 0 = never, 2 = for every size up to 4096 slots (A/B and test runs).
-  const int wave_mode = pdr::option(pdr::OPT_FPS_WAVE);
-  const bool use_wave = wave_mode == 2 || (wave_mode == 1 && static_cast<long>(R) * Q <= 256);
-  // the wave kernel keeps the cloud in N * 16 bytes of dynamic LDS next to its static exchange slots: stay inside
-  // the 64 KiB a launch gets without raising hipFuncAttributeMaxDynamicSharedMemorySize, else the resident kernel
-  const bool wave_fits = static_cast<size_t>(N) * sizeof(float4) + 256 <= 64 * 1024;
-  if (use_wave && wave_fits && static_cast<long>(R) * Q <= 4096) {
-    // rank-ordered slots + packed distances + tree arg-max (fps_wave_kernel): ONE wave while a lane holds <= 4
-    // slots (no barrier at all), four waves (one per SIMD: a single wave issues at most one instruction every
-    // ~4-5 cycles, measured 680 ns per round with 32 slots per lane) above that
-    const long slots = static_cast<long>(R) * Q;
-    if (slots <= 128) return launch_wave<64, 2>(xyz, B, N, m, R, Rbits, Q, idx, s);
-    if (slots <= 256) return launch_wave<64, 4>(xyz, B, N, m, R, Rbits, Q, idx, s);
-    if (slots <= 512) return launch_wave<256, 2>(xyz, B, N, m, R, Rbits, Q, idx, s);
-    if (slots <= 1024) return launch_wave<256, 4>(xyz, B, N, m, R, Rbits, Q, idx, s);
-    if (slots <= 2048) return launch_wave<256, 8>(xyz, B, N, m, R, Rbits, Q, idx, s);
-    return launch_wave<256, 16>(xyz, B, N, m, R, Rbits, Q, idx, s);
-  }
-  // instruction-lean resident kernel (fps_lean_kernel): clouds whose float4 image fits the 64 KiB a launch gets without
-  // raising the dynamic LDS limit, an even number of points per thread.  Option fps_lean = 0: the round-1 resident kernel.
-  const bool lean = pdr::option(pdr::OPT_FPS_LEAN) != 0;
-  if (lean && N > 128 && static_cast<size_t>(N) * sizeof(float4) + 256 <= 64 * 1024) {
-    if (N <= 512) return launch_lean<256, 2>(xyz, B, N, m, R, Rbits, Q, idx, s);
-    if (N <= 1024) return launch_lean<256, 4>(xyz, B, N, m, R, Rbits, Q, idx, s);
-    if (N <= 2048) return launch_lean<256, 8>(xyz, B, N, m, R, Rbits, Q, idx, s);
-    if (N <= 3072) return launch_lean<256, 12>(xyz, B, N, m, R, Rbits, Q, idx, s);
-    return launch_lean<256, 16>(xyz, B, N, m, R, Rbits, Q, idx, s);
-  }
-  static_assert(kMaxResidentN >= 12288, "resident path must cover the LDS-resident range");
-#define PDR_FPS_CASE(T, PPT) \
-  if (N <= (T) * (PPT)) return launch_resident<T, PPT>(xyz, B, N, m, R, Rbits, Q, idx, s)
-  // (512 / 1024 threads per cloud -- fewer points per thread against a wider exchange --, round 5, us per call at B = 32:
-  // 2048->1024 492 / 525 / 885, 1024->256 105 / 124 / 215 for 256 / 512 / 1024 threads: not taken)
-  PDR_FPS_CASE(64, 1);
-  PDR_FPS_CASE(64, 2);
-  PDR_FPS_CASE(256, 1);
-  PDR_FPS_CASE(256, 2);
-  PDR_FPS_CASE(256, 4);
-  PDR_FPS_CASE(256, 8);
-  PDR_FPS_CASE(256, 12);
-  PDR_FPS_CASE(256, 16);
-  PDR_FPS_CASE(1024, 8);
-  PDR_FPS_CASE(1024, 12);
-#undef PDR_FPS_CASE
+  // every instantiation, keyed by what the plan reports
+#define PDR_FPS_RUN(FAMILY, LAUNCH, T_, PPT_)                  \
+  if (p.family == (FAMILY) && p.T == (T_) && p.PPT == (PPT_)) \
+  return LAUNCH<T_, PPT_>(xyz, B, N, m, p.R, p.Rbits, p.Q, idx, s)
+  PDR_FPS_RUN(kFpsWave, launch_wave, 64, 2);
+  PDR_FPS_RUN(kFpsWave, launch_wave, 64, 4);
+  PDR_FPS_RUN(kFpsWave, launch_wave, 256, 2);
+  PDR_FPS_RUN(kFpsWave, launch_wave, 256, 4);
+  PDR_FPS_RUN(kFpsWave, launch_wave, 256, 8);
+  PDR_FPS_RUN(kFpsWave, launch_wave, 256, 16);
+  PDR_FPS_RUN(kFpsLean, launch_lean, 256, 2);
+  PDR_FPS_RUN(kFpsLean, launch_lean, 256, 4);
+  PDR_FPS_RUN(kFpsLean, launch_lean, 256, 8);
+  PDR_FPS_RUN(kFpsLean, launch_lean, 256, 12);
+  PDR_FPS_RUN(kFpsLean, launch_lean, 256, 16);
+  PDR_FPS_RUN(kFpsResident, launch_resident, 64, 1);
+  PDR_FPS_RUN(kFpsResident, launch_resident, 64, 2);
+  PDR_FPS_RUN(kFpsResident, launch_resident, 256, 1);
+  PDR_FPS_RUN(kFpsResident, launch_resident, 256, 2);
+  PDR_FPS_RUN(kFpsResident, launch_resident, 256, 4);
+  PDR_FPS_RUN(kFpsResident, launch_resident, 256, 8);
+  PDR_FPS_RUN(kFpsResident, launch_resident, 256, 12);
+  PDR_FPS_RUN(kFpsResident, launch_resident, 256, 16);
+  PDR_FPS_RUN(kFpsResident, launch_resident, 1024, 8);
+  PDR_FPS_RUN(kFpsResident, launch_resident, 1024, 12);
+#undef PDR_FPS_RUN
   return PDR_EUNSUPPORTED;
 }

@@ -322,27 +322,72 @@ __global__ __launch_bounds__(256) void knn_wave_kernel(const float* __restrict__
   }
 }
 
-// returns true when the wave-per-query kernel took the call
+#ifndef PDR_NN1_QP
+#define PDR_NN1_QP 2     // query PAIRS per thread of the K = 1 kernel (lab builds: -DPDR_NN1_QP=4)
+#endif
+
+// ---- the dispatch decision: ONE host function, read by pdr_knn_points(_ragged), pdr_knn_group and pdr_knn_plan --------
+enum KnnFamily { kKnnNone = -1, kKnnThread = 0, kKnnWave = 1, kKnnPacked = 2 };
+
+struct KnnPlan {
+  int family;   // kKnnNone: an empty call, nothing is launched
+  int param;    // thread-per-query: KMAX; wave-per-query: NCH (cloud slots per lane); packed K = 1: QP (query pairs)
+  int qpw;      // wave-per-query: queries per wave; 0 elsewhere
+  int gx;       // workgroups per cloud (grid.x)
+};
+
+// group = 0: pdr_knn_points (has_nn: the gathered neighbours are asked for); group = 1: pdr_knn_group.  Returns the
+// refusals of those calls that do not depend on a pointer.
+int plan_knn(int B, int n1, int n2, int K, bool has_nn, bool group, KnnPlan* p) {
+  if (group) {
+    if (B < 0 || n1 < 0 || n2 <= 0 || K <= 0 || K > n2) return PDR_EINVAL;
+    if (K > 16) return PDR_EUNSUPPORTED;
+  } else {
+    if (B < 0 || n1 < 0 || n2 < 0 || K <= 0) return PDR_EINVAL;
+    if (K > 32) return PDR_EUNSUPPORTED;
+  }
+  p->family = kKnnNone, p->param = 0, p->qpw = 0, p->gx = 0;
+  if (B == 0 || n1 == 0) return PDR_OK;
+  if (!group && K == 1 && !has_nn && n2 > 0) {
+    // dedicated packed-math kernel (one direction of pdr_chamfer_nn); bit-identical results
+    p->family = kKnnPacked, p->param = PDR_NN1_QP;
+    p->gx = (n1 + 256 * 2 * PDR_NN1_QP - 1) / (256 * 2 * PDR_NN1_QP);
+    return PDR_OK;
+  }
+  const bool wave_k = group || (K > 1 && K <= n2);   // (pdr_knn_group has K <= n2 and no K = 1 kernel of its own)
+  if (wave_k && pdr::option(pdr::OPT_KNN_WAVE) != 0 && K <= 8 && n2 >= 64 && n2 <= 1024) {
+    // queries per wave: amortise the register fill of the cloud while the launch keeps >= 1024 workgroups (measured
+    // at 2048 x 1024, B = 32: 4 / 8 / 16 queries per wave 60.6 / 60.1 / 60.3 us, 32: 88.6 us)
+    int qpw = 16;
+    while (qpw > 1 && static_cast<long long>(B) * ((n1 + 4 * qpw - 1) / (4 * qpw)) < 1024) qpw >>= 1;
+    p->family = kKnnWave, p->qpw = qpw, p->gx = (n1 + 4 * qpw - 1) / (4 * qpw);
+    p->param = n2 <= 64 ? 1 : n2 <= 128 ? 2 : n2 <= 256 ? 4 : n2 <= 512 ? 8 : 16;
+    return PDR_OK;
+  }
+  p->family = kKnnThread, p->gx = (n1 + 255) / 256;
+  p->param = (K == 1 && !group) ? 1 : K <= 4 ? 4 : K <= 8 ? 8 : K <= 16 ? 16 : 32;
+  return PDR_OK;
+}
+
 template <typename IdxT, bool RAGGED = false>
-bool launch_knn_wave(const float* x, const float* y, int B, int n1, int n2, int K, float* dists, IdxT* idx, float* nn,
-                     float* wgt, hipStream_t s, const int64_t* len1 = nullptr, const int64_t* len2 = nullptr) {
-  const bool on = pdr::option(pdr::OPT_KNN_WAVE) != 0;
-  if (!on || K > 8 || n2 < 64 || n2 > 1024) return false;
-  // queries per wave: amortise the register fill of the cloud while the launch keeps >= 1024 workgroups (measured at
-  // 2048 x 1024, B = 32: 4 / 8 / 16 queries per wave 60.6 / 60.1 / 60.3 us, 32: 88.6 us)
-  int qpw = 16;
-  while (qpw > 1 && static_cast<long long>(B) * ((n1 + 4 * qpw - 1) / (4 * qpw)) < 1024) qpw >>= 1;
-  const dim3 grid((n1 + 4 * qpw - 1) / (4 * qpw), B);
+int launch_knn_wave(const KnnPlan& p, const float* x, const float* y, int B, int n1, int n2, int K, float* dists,
+                    IdxT* idx, float* nn, float* wgt, hipStream_t s, const int64_t* len1 = nullptr,
+                    const int64_t* len2 = nullptr) {
+  const dim3 grid(p.gx, B);
 #define PDR_KW(NCH)                                                                                                  \
-  hipLaunchKernelGGL((knn_wave_kernel<NCH, IdxT, RAGGED>), grid, dim3(256), 0, s, x, y, n1, n2, K, qpw, dists, idx, nn, \
-                     wgt, len1, len2)
-  if (n2 <= 64) PDR_KW(1);
-  else if (n2 <= 128) PDR_KW(2);
-  else if (n2 <= 256) PDR_KW(4);
-  else if (n2 <= 512) PDR_KW(8);
-  else PDR_KW(16);
+  case NCH:                                                                                                          \
+    hipLaunchKernelGGL((knn_wave_kernel<NCH, IdxT, RAGGED>), grid, dim3(256), 0, s, x, y, n1, n2, K, p.qpw, dists, idx, \
+                       nn, wgt, len1, len2);                                                                         \
+    return pdr::check_launch()
+  switch (p.param) {
+    PDR_KW(1);
+    PDR_KW(2);
+    PDR_KW(4);
+    PDR_KW(8);
+    PDR_KW(16);
+  }
 #undef PDR_KW
-  return true;
+  return PDR_EUNSUPPORTED;
 }
 
 // ---- K = 1 (Chamfer) ------------------------------------------------------------------------
@@ -469,10 +514,6 @@ __global__ __launch_bounds__(256) void nn1_kernel(const float* __restrict__ xa, 
   }
 }
 
-#ifndef PDR_NN1_QP
-#define PDR_NN1_QP 2     // query PAIRS per thread of the K = 1 kernel (lab builds: -DPDR_NN1_QP=4)
-#endif
-
 template <int K, bool RAGGED>
 int launch_knn(const float* x, const float* y, const int64_t* len1, const int64_t* len2, int B, int n1, int n2,
                int Kout, float* dists, int64_t* idx, float* nn, hipStream_t s) {
@@ -486,26 +527,27 @@ int launch_knn(const float* x, const float* y, const int64_t* len1, const int64_
 template <bool RAGGED>
 int knn_points(const float* x, const float* y, const int64_t* len1, const int64_t* len2, int B, int n1, int n2, int K,
                float* dists, int64_t* idx, float* nn, pdr_stream_t stream) {
-  if (B < 0 || n1 < 0 || n2 < 0 || K <= 0) return PDR_EINVAL;
-  if (K > 32) return PDR_EUNSUPPORTED;
-  if (B == 0 || n1 == 0) return PDR_OK;
+  KnnPlan p;
+  const int rc = plan_knn(B, n1, n2, K, nn != nullptr, false, &p);
+  if (rc != PDR_OK) return rc;
+  if (p.family == kKnnNone) return PDR_OK;
   if (!x || !dists || !idx || (n2 > 0 && !y)) return PDR_EINVAL;
   hipStream_t s = pdr::as_stream(stream);
-  if (K == 1 && !nn && n2 > 0) {
-    // dedicated packed-math kernel (one direction of pdr_chamfer_nn); bit-identical results
-    constexpr int QPB = 256 * 2 * PDR_NN1_QP;   // queries per workgroup
-    hipLaunchKernelGGL((nn1_kernel<PDR_NN1_QP, int64_t, RAGGED>), dim3((n1 + QPB - 1) / QPB, B, 1), dim3(256), 0, s, x,
-                       y, n1, n2, dists, idx, static_cast<float*>(nullptr), static_cast<int64_t*>(nullptr), len1, len2,
-                       -1);
+  if (p.family == kKnnPacked) {
+    hipLaunchKernelGGL((nn1_kernel<PDR_NN1_QP, int64_t, RAGGED>), dim3(p.gx, B, 1), dim3(256), 0, s, x, y, n1, n2, dists,
+                       idx, static_cast<float*>(nullptr), static_cast<int64_t*>(nullptr), len1, len2, -1);
     return pdr::check_launch();
   }
-  if (K == 1) return launch_knn<1, RAGGED>(x, y, len1, len2, B, n1, n2, K, dists, idx, nn, s);
-  if (K <= n2 && launch_knn_wave<int64_t, RAGGED>(x, y, B, n1, n2, K, dists, idx, nn, nullptr, s, len1, len2))
-    return pdr::check_launch();
-  if (K <= 4) return launch_knn<4, RAGGED>(x, y, len1, len2, B, n1, n2, K, dists, idx, nn, s);
-  if (K <= 8) return launch_knn<8, RAGGED>(x, y, len1, len2, B, n1, n2, K, dists, idx, nn, s);
-  if (K <= 16) return launch_knn<16, RAGGED>(x, y, len1, len2, B, n1, n2, K, dists, idx, nn, s);
-  return launch_knn<32, RAGGED>(x, y, len1, len2, B, n1, n2, K, dists, idx, nn, s);
+  if (p.family == kKnnWave)
+    return launch_knn_wave<int64_t, RAGGED>(p, x, y, B, n1, n2, K, dists, idx, nn, nullptr, s, len1, len2);
+  switch (p.param) {
+    case 1: return launch_knn<1, RAGGED>(x, y, len1, len2, B, n1, n2, K, dists, idx, nn, s);
+    case 4: return launch_knn<4, RAGGED>(x, y, len1, len2, B, n1, n2, K, dists, idx, nn, s);
+    case 8: return launch_knn<8, RAGGED>(x, y, len1, len2, B, n1, n2, K, dists, idx, nn, s);
+    case 16: return launch_knn<16, RAGGED>(x, y, len1, len2, B, n1, n2, K, dists, idx, nn, s);
+    case 32: return launch_knn<32, RAGGED>(x, y, len1, len2, B, n1, n2, K, dists, idx, nn, s);
+  }
+  return PDR_EUNSUPPORTED;
 }
 
 // pdr_chamfer_nn and pdr_chamfer_nn_ragged: both directions in one launch
@@ -573,21 +615,39 @@ extern "C" int pdr_chamfer_nn_ragged(const float* x, const float* y, const int64
 // interpolation weights of :500-503 in the same pass.  Requires K <= n2 (no padding slots).
 extern "C" int pdr_knn_group(const float* x, const float* y, int B, int n1, int n2, int K, float* dists,
                              int* idx, float* weights, pdr_stream_t stream) {
-  if (B < 0 || n1 < 0 || n2 <= 0 || K <= 0 || K > n2) return PDR_EINVAL;
-  if (K > 16) return PDR_EUNSUPPORTED;
-  if (B == 0 || n1 == 0) return PDR_OK;
+  KnnPlan p;
+  const int rc = plan_knn(B, n1, n2, K, false, true, &p);
+  if (rc != PDR_OK) return rc;
+  if (p.family == kKnnNone) return PDR_OK;
   if (!x || !y || !dists || !idx || !weights) return PDR_EINVAL;
   hipStream_t s = pdr::as_stream(stream);
-  if (launch_knn_wave<int>(x, y, B, n1, n2, K, dists, idx, nullptr, weights, s)) return pdr::check_launch();
-  const dim3 grid((n1 + 255) / 256, B);
-#define PDR_KG(KK)                                                                                      \
-  hipLaunchKernelGGL((nn_search_kernel<KK, kAcc3, int, false>), grid, dim3(256), 0, s, x, y, n1, n2, K,  \
-                     dists, idx, static_cast<float*>(nullptr), weights)
-  if (K <= 4) PDR_KG(4);
-  else if (K <= 8) PDR_KG(8);
-  else PDR_KG(16);
+  if (p.family == kKnnWave) return launch_knn_wave<int>(p, x, y, B, n1, n2, K, dists, idx, nullptr, weights, s);
+  const dim3 grid(p.gx, B);
+#define PDR_KG(KK)                                                                                        \
+  case KK:                                                                                                \
+    hipLaunchKernelGGL((nn_search_kernel<KK, kAcc3, int, false>), grid, dim3(256), 0, s, x, y, n1, n2, K,  \
+                       dists, idx, static_cast<float*>(nullptr), weights);                                \
+    return pdr::check_launch()
+  switch (p.param) {
+    PDR_KG(4);
+    PDR_KG(8);
+    PDR_KG(16);
+  }
 #undef PDR_KG
-  return pdr::check_launch();
+  return PDR_EUNSUPPORTED;
+}
+
+// Which kernel pdr_knn_points (group = 0; has_nn: `nn` is asked for) or pdr_knn_group (group = 1) runs for these sizes
+// under the current knn_wave option, and the refusals of those calls that do not depend on a pointer (host only):
+// out = {family (0 thread per query, 1 wave per query, 2 packed K = 1, -1 empty call: no launch), the kernel's template
+// parameter (KMAX, NCH or QP), queries per wave (0 where it does not apply), workgroups per cloud}.
+extern "C" int pdr_knn_plan(int B, int n1, int n2, int K, int has_nn, int group, int out[4]) {
+  if (!out) return PDR_EINVAL;
+  KnnPlan p;
+  const int rc = plan_knn(B, n1, n2, K, has_nn != 0, group != 0, &p);
+  if (rc != PDR_OK) return rc;
+  out[0] = p.family, out[1] = p.param, out[2] = p.qpw, out[3] = p.gx;
+  return PDR_OK;
 }
 
 // ---- kNN backward (pytorch3d knn_points backward, norm 2; cf. chamfer3D.cu:155-195 for K = 1) ----
