@@ -62,7 +62,8 @@ typedef void *pdr_stream_t; /* hipStream_t */
  *                pdr_fused_layer_pair are new; pdr_knn_points_ragged / pdr_chamfer_nn_ragged are new; pdr_approxmatch_ragged /
  *                pdr_emd_cost_ragged / pdr_matchcost_ragged / pdr_matchcost_grad_ragged are new; pdr_emd_cost_grad /
  *                pdr_emd_cost_grad_ragged are new; pdr_chamfer_pairwise is new; pdr_fps_plan / pdr_knn_plan /
- *                pdr_ball_query_plan (host-only dispatch queries) are new. */
+ *                pdr_ball_query_plan (host-only dispatch queries) are new; pdr_gather_plan (the same for
+ *                pdr_gather_add* / pdr_gather_moments*) is new. */
 int pdr_version(void);
 /* last hip error string seen by this thread after a PDR_ELAUNCH ("" if none) */
 const char *pdr_last_error(void);
@@ -644,6 +645,35 @@ int pdr_gather_moments_tiles_twin(const float *U, int ldu, int n_src, const floa
                                   float *partial, int relu_col0, int win0_col0, int win0_cols, int win1_col0,
                                   int win1_cols, const unsigned char *tile_valid, int partial_tpb, const int *idx0,
                                   float *Yd, int ldyd, const int *wrow0, float wmul, pdr_stream_t stream);
+/* Host-only (nothing is launched, no pointer exists): what pdr_gather_add* / pdr_gather_moments* launch for these sizes,
+ * windows and pointers -- the decision of the ONE host function their launch path reads, with the same return code as
+ * the call for every refusal that does not depend on a pointer's value.  flags: which optional pointers the call
+ * carries; a pointer that goes with a flagged one (V0 with counts, r1 with s1, r2 with s2, Yd and wrow0 with idx0) and
+ * every required pointer count as given and 16-byte aligned.  The windows of pdr_gather_add* are (0, Cout, 0, 0); ldy /
+ * ycol0 / ycols are read with PDR_GATHER_HAS_Y only, partial_tpb with _TILES / _TWIN, ldyd with _TWIN.  out (24 ints;
+ * all 0 for a refused or an empty (B = 0) call):
+ *   [0]  lanes per row LPR: 16 (Cout <= 64) / 32 (Cout <= 128) / 64      [1]  KPOW2: K a power of two <= 32
+ *   [2]  HAS_S: s1 or s2                [3]  HAS_EM: counts              [4]  YWIN: a Y is written
+ *   [5]  statistics (partial != NULL)   [6]  the main tiles walk one V row per query: KPOW2 and K >= out[7]
+ *   [7]  rows a wave walks per iteration with this LPR (16 / 8 / 4)
+ *   [8]..[11]  the windows as walked: first column and length of the first, of the second (length 0: one window)
+ *   [12] float4 pieces of the windows   [13] column passes = ceil([12] / LPR)
+ *   [14] grid.x = [16] + [17]           [15] grid.y: [13] when the passes are dealt to workgroups ([14] <= 1024 and
+ *        [13] > 1), else 1: every workgroup walks its tile's passes one after the other
+ *   [16] main tiles = B [18]            [17] twin tiles = B [19]
+ *   [18] 128-row tiles per cloud        [19] twin tiles per cloud = ceil(rows_per_batch / K / 128); 0: no twin form
+ *   [20] [21] the written window of Y: first column, length padded to 4 (0: no Y)
+ *   [22] a tile subset is walked        [23] 0 (reserved) */
+#define PDR_GATHER_HAS_COUNTS 1u
+#define PDR_GATHER_HAS_S1 2u
+#define PDR_GATHER_HAS_S2 4u
+#define PDR_GATHER_HAS_Y 8u
+#define PDR_GATHER_HAS_PARTIAL 16u
+#define PDR_GATHER_HAS_TILES 32u /* tile_valid */
+#define PDR_GATHER_HAS_TWIN 64u  /* idx0 / Yd / wrow0: pdr_gather_*_tiles_twin */
+int pdr_gather_plan(int B, int n_src, int rows_per_batch, int K, int Cout, int ldu, int ldv, int ldy, int ycol0,
+                    int ycols, int win0_col0, int win0_cols, int win1_col0, int win1_cols, int partial_tpb, int ldyd,
+                    unsigned flags, int out[24]);
 /* Moments of a materialised (B*rpb, C) tensor with one weight per row, appended to the moments of a tile subset:
  * partial row b*ptpb + tpb_full + j  <-  sum_r w[r] f, sum_r w[r] f^2 over the rows r of 128-row tile j of batch
  * element b (f = y, columns >= relu_col0: max(y,0)); partial rows b*ptpb + t (t < tpb_full) of the tiles with

@@ -93,6 +93,7 @@ SIGNATURES = {
                                       _I, _P, _I, _P]),
     "pdr_gather_moments_tiles_twin": (_I, [_P, _I, _I, _P, _P, _I, _P, _P, _I, _I, _I, _I, _P, _I, _I, _I, _I, _I, _P,
                                            _I, _P, _P, _I, _P, _F, _P]),
+    "pdr_gather_plan": (_I, [_I] * 16 + [_c.c_uint, _P]),
     "pdr_dedup_plan": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
     "pdr_dedup_sort": (_I, [_P, _I, _I, _P, _P, _P, _P]),
     "pdr_weighted_moments": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _I, _I, _P, _P]),

@@ -440,6 +440,21 @@ extern "C" int pdr_gather_rows(const float* src, const int* idx, int B, int n, i
 // launch + pdr_weighted_moments produced, in the launch that walks the tile subset.
 typedef float pdr_f2 __attribute__((ext_vector_type(2)));
 
+// How a wave walks its 32 rows with LPR lanes per row -- read by gather_tile AND by plan_gather, so that the plan's
+// `shared` threshold cannot drift from the kernel's.  rpi: rows per wave instruction.  depth: row groups in flight per
+// iteration -- the kernel is bound by the latency of its L2 gathers, so every wave keeps `depth` independent 16-byte U
+// loads outstanding (4 measured against 2; the order of a column's sum does not depend on it; 8 for LPR 64 measured
+// 0-10 % slower than 4: DESIGN.md 4.11).  shared_rows = depth x rpi rows per iteration: a power-of-two K >= that many
+// rows takes the one-V-row-per-query walk (16 / 8 / 4 for LPR 16 / 32 / 64).
+struct GatherWalk {
+  int rpi, depth, shared_rows;
+};
+constexpr GatherWalk gather_walk(int lpr) {
+  const int rpi = 64 / lpr;
+  const int depth = 32 / rpi < 4 ? 32 / rpi : 4;
+  return {rpi, depth, depth * rpi};
+}
+
 template <bool YWIN>
 struct YWindow {};
 template <>
@@ -464,11 +479,8 @@ __device__ __forceinline__ void gather_tile(
     float (*red)[4 * LPR][2]) {
   static_assert(!(TWIN && YWIN), "a twin tile writes tw.Y whole, never a window");
   constexpr int TM = 128;
-  constexpr int RPI = 64 / LPR;            // rows per wave instruction
-  // row groups in flight per iteration: the kernel is bound by the latency of its L2 gathers, so every wave keeps
-  // DEPTH independent 16-byte U loads outstanding (4 measured against 2; the order of a column's sum does not depend on
-  // it; 8 for LPR 64 measured 0-10 % slower than 4: DESIGN.md 4.11)
-  constexpr int DEPTH = 32 / RPI < 4 ? 32 / RPI : 4;
+  constexpr int RPI = gather_walk(LPR).rpi;       // rows per wave instruction
+  constexpr int DEPTH = gather_walk(LPR).depth;   // row groups in flight per iteration (gather_walk)
   constexpr int CW = 4 * LPR;              // columns covered per pass
   const int rows_per_batch = TWIN ? rows_per_batch_ / K_ : rows_per_batch_;
   const int K = TWIN ? 1 : K_;
@@ -611,7 +623,7 @@ __device__ __forceinline__ void gather_tile(
       }
     };
     bool shared = false;                                           // uniform
-    if constexpr (KPOW2 && !TWIN) shared = K >= DEPTH * RPI;
+    if constexpr (KPOW2 && !TWIN) shared = K >= gather_walk(LPR).shared_rows;
     if constexpr (YWIN) {
       if (!partial) {              // Y only: nothing is accumulated, folded or waited for (uniform: no barrier is missed)
         if (!shared) walk_rows(std::false_type{}, std::false_type{}, std::false_type{});
@@ -685,7 +697,97 @@ __global__ __launch_bounds__(256) void gather_kernel(
                                                       K, Cout, partial, relu_col0, mw, tile_valid, partial_tpb, tw, yw, red);
 }
 
-// The one launch path of pdr_gather_add* / pdr_gather_moments*.
+// ---- the dispatch decision: ONE host function, read by gather_launch below and by pdr_gather_plan ---------------------
+// What plan_gather reads of a call: its sizes, its windows and WHICH pointers are there (and whether they are 16-byte
+// aligned) -- never what a pointer points to.
+struct GatherCall {
+  int B, n_src, rows_per_batch, K, Cout, ldu, ldv, ldy, ycol0, ycols;
+  int win0_col0, win0_cols, win1_col0, win1_cols, partial_tpb, ldyd;
+  bool required;                 // U, V and idx
+  bool counts, V0, s1, r1, s2, r2, Y, partial, tile_valid;
+  bool idx0, Yd, wrow0;          // the twin form's pointers
+  bool aligned, Yd_aligned;      // U, V, V0, Y, r1, r2 (those present) / Yd
+};
+
+struct GatherPlan {
+  int lpr;                       // lanes per row: 16 / 32 / 64; 0: an empty call (B = 0), nothing is launched
+  bool kpow2, has_s, has_em, ywin;   // the instantiation gather_kernel<LPR, KPOW2, HAS_S, HAS_EM, YWIN>
+  bool stats;                    // partial != NULL (false: the Y-only walk, no fold, no barrier)
+  bool shared;                   // the main tiles walk one V row per query (kpow2 and K >= shared_rows)
+  int shared_rows;               // gather_walk(lpr).shared_rows
+  pdr::MomentWindows mw;         // the windows as walked
+  int w4, passes;                // float4 pieces of the windows; column passes of lpr pieces
+  int grid_x, grid_y;            // grid.y = passes when they are dealt to workgroups, else 1 (walked in the workgroup)
+  int n_main, tpb;               // main tiles (B tpb) and per cloud
+  int n_twin, twin_tpb;          // twin tiles (grid_x - n_main) and per cloud; 0 without the twin form
+  int ycol0, y4;                 // the written window [ycol0, ycol0 + y4) (padded to float4); y4 = 0 without a Y
+  bool tiles;                    // a tile subset is walked
+};
+
+// Every return code of pdr_gather_add* / pdr_gather_moments* that is decided behind their NULL checks of tile_valid /
+// idx0, in the order the calls have always decided them.  The windows of pdr_gather_add* are the whole width
+// (0, Cout, 0, 0).
+static int plan_gather(const GatherCall& a, GatherPlan* p) {
+  *p = GatherPlan{};
+  if (!a.required || (!a.Y && !a.partial) || a.B < 0 || a.rows_per_batch <= 0 || a.K <= 0 || a.Cout <= 0 || a.n_src <= 0)
+    return PDR_EINVAL;
+  const int tpb = (a.rows_per_batch + 127) / 128;
+  // (the entry points with a tile subset refuse these whatever B is: the twin form rows that are no whole queries, the
+  // plain subset form a partial stride below the tiles of a cloud -- the twin form's stride is checked below)
+  if (a.idx0 && (!a.tile_valid || a.rows_per_batch % a.K != 0)) return PDR_EINVAL;
+  if (a.tile_valid && !a.idx0 && a.partial_tpb < tpb) return PDR_EINVAL;
+  // windows: inside [0, Cout), ascending, disjoint
+  if (a.win0_col0 < 0 || a.win0_cols <= 0 || a.win0_cols > a.Cout - a.win0_col0) return PDR_EINVAL;
+  if (a.win1_cols < 0 ||
+      (a.win1_cols > 0 && (a.win1_col0 < a.win0_col0 + a.win0_cols || a.win1_cols > a.Cout - a.win1_col0)))
+    return PDR_EINVAL;
+  if (a.B == 0) return PDR_OK;
+  if (a.rows_per_batch % a.K != 0 || (a.counts && !a.V0) || (a.s1 && !a.r1) || (a.s2 && !a.r2)) return PDR_EINVAL;
+  const int c4 = (a.Cout + 3) & ~3;
+  const int ycols = a.ycols < 0 ? a.Cout - a.ycol0 : a.ycols;   // -1: every column from ycol0 on
+  // the written window [ycol0, ycol0 + ycols) starts on a float4 boundary; Y holds it from column 0
+  if (a.Y && (a.ycol0 < 0 || a.ycol0 % 4 || ycols <= 0 || a.ycol0 + ycols > a.Cout)) return PDR_EINVAL;
+  const int y4 = (ycols + 3) & ~3;
+  if (a.ldu % 4 || a.ldv % 4 || a.ldu < c4 || a.ldv < c4 || (a.Y && (a.ldy % 4 || a.ldy < y4))) return PDR_EINVAL;
+  // rows are moved as float4: every base pointer (possibly offset to a column sub-range) 16-B aligned
+  if (!a.aligned) return PDR_EINVAL;
+  const bool has_s = a.s1 || a.s2;
+  long nblocks = static_cast<long>(a.B) * tpb;
+  p->n_main = static_cast<int>(nblocks);
+  if (a.idx0) {
+    // twin blocks: the per-query rows (rows_per_batch / K per cloud) behind the main tiles
+    const int mq = a.rows_per_batch / a.K;
+    if (!a.Yd || !a.wrow0 || !a.partial || has_s || a.ldyd % 4 || a.ldyd < c4 || !a.Yd_aligned ||
+        a.partial_tpb < tpb + (mq + 127) / 128)
+      return PDR_EINVAL;
+    p->twin_tpb = (mq + 127) / 128;
+    nblocks += static_cast<long>(a.B) * p->twin_tpb;
+  }
+  if (nblocks >= (1L << 31)) return PDR_EINVAL;
+  // rows move as float4 pieces: a window starts on one (the caller keeps the whole width for the others)
+  if (a.win0_col0 % 4 || (a.win1_cols > 0 && a.win1_col0 % 4)) return PDR_EUNSUPPORTED;
+  p->mw = pdr::MomentWindows{a.win0_col0, a.win0_cols, a.win1_cols > 0 ? a.win1_col0 : a.win0_col0 + a.win0_cols,
+                             a.win1_cols > 0 ? a.win1_cols : 0};
+  // lanes per row from the FULL width, whatever is walked: what keeps the order of every column's sum
+  p->lpr = a.Cout <= 64 ? 16 : (a.Cout <= 128 ? 32 : 64);
+  p->kpow2 = (a.K & (a.K - 1)) == 0 && a.K <= 32;
+  p->has_s = has_s, p->has_em = a.counts, p->ywin = a.Y, p->stats = a.partial, p->tiles = a.tile_valid;
+  p->shared_rows = p->lpr == 16 ? gather_walk(16).shared_rows
+                                : (p->lpr == 32 ? gather_walk(32).shared_rows : gather_walk(64).shared_rows);
+  p->shared = p->kpow2 && a.K >= p->shared_rows;
+  // column passes per workgroup: all of them, unless the launch has fewer tiles than the chip holds workgroups
+  p->w4 = (p->mw.na + 3) / 4 + (p->mw.nb + 3) / 4;
+  p->passes = (p->w4 + p->lpr - 1) / p->lpr;
+  p->grid_x = static_cast<int>(nblocks);
+  p->grid_y = (nblocks <= 1024 && p->passes > 1) ? p->passes : 1;
+  p->tpb = tpb;
+  p->n_twin = p->grid_x - p->n_main;
+  p->ycol0 = a.Y ? a.ycol0 : 0;
+  p->y4 = a.Y ? y4 : 0;
+  return PDR_OK;
+}
+
+// The one launch path of pdr_gather_add* / pdr_gather_moments*: it launches what plan_gather names.
 // Y (B*rows_per_batch, columns [ycol0, ycol0 + ycols) of Cout; ld ldy) = U[b, idx[p]] + V[p / K] (+ s1[p] r1 + s2[p] r2),
 // empty balls -> V0; NULL: statistics only.  U (B, n_src, ldu), V / V0 (B*rows_per_batch/K, ldv); all leading dimensions
 // multiples of 4, 16-B aligned.  partial: NULL (with a Y) or (B * ceil(rows_per_batch / 128), Cout, 2) moments as in
@@ -698,80 +800,79 @@ static int gather_launch(const float* U, int ldu, int n_src, const float* V, con
                          const unsigned char* tile_valid, int partial_tpb, pdr_stream_t stream,
                          const int* idx0 = nullptr, float* Yd = nullptr, int ldyd = 0, const int* wrow0 = nullptr,
                          float wmul = 1.0f) {
-  if (!U || !V || !idx || (!Y && !partial) || B < 0 || rows_per_batch <= 0 || K <= 0 || Cout <= 0 || n_src <= 0)
-    return PDR_EINVAL;
-  // windows: inside [0, Cout), ascending, disjoint
-  if (win0_col0 < 0 || win0_cols <= 0 || win0_cols > Cout - win0_col0) return PDR_EINVAL;
-  if (win1_cols < 0 || (win1_cols > 0 && (win1_col0 < win0_col0 + win0_cols || win1_cols > Cout - win1_col0)))
-    return PDR_EINVAL;
-  if (B == 0) return PDR_OK;
-  if (rows_per_batch % K != 0 || (counts && !V0) || (s1 && !r1) || (s2 && !r2)) return PDR_EINVAL;
-  const int c4 = (Cout + 3) & ~3;
-  if (ycols < 0) ycols = Cout - ycol0;                     // -1: every column from ycol0 on
-  // the written window [ycol0, ycol0 + ycols) starts on a float4 boundary; Y holds it from column 0
-  if (Y && (ycol0 < 0 || ycol0 % 4 || ycols <= 0 || ycol0 + ycols > Cout)) return PDR_EINVAL;
-  const int y4 = (ycols + 3) & ~3;
-  if (ldu % 4 || ldv % 4 || ldu < c4 || ldv < c4 || (Y && (ldy % 4 || ldy < y4))) return PDR_EINVAL;
-  // rows are moved as float4: every base pointer (possibly offset to a column sub-range) 16-B aligned
   auto al = [](const void* q) { return reinterpret_cast<uintptr_t>(q) % 16 == 0; };
-  if (!al(U) || !al(V) || (V0 && !al(V0)) || (Y && !al(Y)) || (r1 && !al(r1)) || (r2 && !al(r2)))
-    return PDR_EINVAL;
-  const int tpb = (rows_per_batch + 127) / 128;
-  const bool kpow2 = (K & (K - 1)) == 0 && K <= 32;
-  const bool has_s = s1 != nullptr || s2 != nullptr;
-  pdr::GatherTwin tw{idx0, Yd, wrow0, ldyd, 0, wmul};
-  long nblocks = static_cast<long>(B) * tpb;
-  if (idx0) {
-    // twin blocks: the per-query rows (rows_per_batch / K per cloud) behind the main tiles
-    const int mq = rows_per_batch / K;
-    if (!Yd || !wrow0 || !partial || has_s || ldyd % 4 || ldyd < c4 || !al(Yd) ||
-        partial_tpb < tpb + (mq + 127) / 128)
-      return PDR_EINVAL;
-    tw.n_main = static_cast<int>(nblocks);
-    nblocks += static_cast<long>(B) * ((mq + 127) / 128);
-  }
-  if (nblocks >= (1L << 31)) return PDR_EINVAL;
-  // rows move as float4 pieces: a window starts on one (the caller keeps the whole width for the others)
-  if (win0_col0 % 4 || (win1_cols > 0 && win1_col0 % 4)) return PDR_EUNSUPPORTED;
-  const pdr::MomentWindows mw{win0_col0, win0_cols, win1_cols > 0 ? win1_col0 : win0_col0 + win0_cols,
-                              win1_cols > 0 ? win1_cols : 0};
-  // lanes per row from the FULL width, whatever is walked: what keeps the order of every column's sum
-  const int lpr = Cout <= 64 ? 16 : (Cout <= 128 ? 32 : 64);
-  // column passes per workgroup: all of them, unless the launch has fewer tiles than the chip holds workgroups
-  const int w4 = (mw.na + 3) / 4 + (mw.nb + 3) / 4;
-  const int passes = (w4 + lpr - 1) / lpr;
-  const int ncb = (nblocks <= 1024 && passes > 1) ? passes : 1;
-  const dim3 grid(static_cast<unsigned>(nblocks), static_cast<unsigned>(ncb));
+  GatherCall a{};
+  a.B = B, a.n_src = n_src, a.rows_per_batch = rows_per_batch, a.K = K, a.Cout = Cout, a.ldu = ldu, a.ldv = ldv;
+  a.ldy = ldy, a.ycol0 = ycol0, a.ycols = ycols, a.win0_col0 = win0_col0, a.win0_cols = win0_cols;
+  a.win1_col0 = win1_col0, a.win1_cols = win1_cols, a.partial_tpb = partial_tpb, a.ldyd = ldyd;
+  a.required = U && V && idx;
+  a.counts = counts, a.V0 = V0, a.s1 = s1, a.r1 = r1, a.s2 = s2, a.r2 = r2, a.Y = Y, a.partial = partial;
+  a.tile_valid = tile_valid, a.idx0 = idx0, a.Yd = Yd, a.wrow0 = wrow0;
+  a.aligned = al(U) && al(V) && al(V0) && al(Y) && al(r1) && al(r2);   // (a NULL pointer counts as aligned)
+  a.Yd_aligned = al(Yd);
+  GatherPlan p;
+  const int rc = plan_gather(a, &p);
+  if (rc != PDR_OK || p.lpr == 0) return rc;
+  const pdr::GatherTwin tw{idx0, Yd, wrow0, ldyd, p.n_twin > 0 ? p.n_main : 0, wmul};
+  const pdr::MomentWindows mw = p.mw;
+  const dim3 grid(static_cast<unsigned>(p.grid_x), static_cast<unsigned>(p.grid_y));
   hipStream_t st = pdr::as_stream(stream);
 #define PDR_G_Y(LPR, KP, HS, HE, YW)                                                                                  \
   hipLaunchKernelGGL((gather_kernel<LPR, KP, HS, HE, YW>), grid, dim3(256), 0, st, U, ldu, n_src, V, V0, ldv, idx,    \
                      counts, s1, r1, s2, r2, rows_per_batch, K, Cout, partial, relu_col0, mw, tile_valid, partial_tpb, \
-                     tw, y_window<YW>(Y, ldy, ycol0, ycol0 + y4))
+                     tw, y_window<YW>(Y, ldy, p.ycol0, p.ycol0 + p.y4))
 #define PDR_G_E(LPR, KP, HS, HE)              \
   do {                                        \
-    if (Y) PDR_G_Y(LPR, KP, HS, HE, true);    \
+    if (p.ywin) PDR_G_Y(LPR, KP, HS, HE, true);    \
     else PDR_G_Y(LPR, KP, HS, HE, false);     \
   } while (0)
 #define PDR_G_K(LPR, KP, HS)                  \
   do {                                        \
-    if (counts) PDR_G_E(LPR, KP, HS, true);   \
+    if (p.has_em) PDR_G_E(LPR, KP, HS, true);   \
     else PDR_G_E(LPR, KP, HS, false);         \
   } while (0)
 #define PDR_G(LPR)                                        \
   do {                                                    \
-    if (kpow2 && has_s) PDR_G_K(LPR, true, true);         \
-    else if (kpow2) PDR_G_K(LPR, true, false);            \
-    else if (has_s) PDR_G_K(LPR, false, true);            \
+    if (p.kpow2 && p.has_s) PDR_G_K(LPR, true, true);     \
+    else if (p.kpow2) PDR_G_K(LPR, true, false);          \
+    else if (p.has_s) PDR_G_K(LPR, false, true);          \
     else PDR_G_K(LPR, false, false);                      \
   } while (0)
-  if (lpr == 16) PDR_G(16);
-  else if (lpr == 32) PDR_G(32);
+  if (p.lpr == 16) PDR_G(16);
+  else if (p.lpr == 32) PDR_G(32);
   else PDR_G(64);
 #undef PDR_G
 #undef PDR_G_K
 #undef PDR_G_E
 #undef PDR_G_Y
   return pdr::check_launch();
+}
+
+// Host only: what a call with these sizes, windows and pointers would launch.  flags: PDR_GATHER_HAS_* of pdr_hip.h; a
+// pointer that goes with a flagged one (V0 with counts, r1 / r2 with s1 / s2, Yd and wrow0 with idx0) and every
+// required pointer count as given and aligned.
+extern "C" int pdr_gather_plan(int B, int n_src, int rows_per_batch, int K, int Cout, int ldu, int ldv, int ldy,
+                               int ycol0, int ycols, int win0_col0, int win0_cols, int win1_col0, int win1_cols,
+                               int partial_tpb, int ldyd, unsigned flags, int out[24]) {
+  if (!out || (flags & ~0x7fu)) return PDR_EINVAL;
+  GatherCall a{};
+  a.B = B, a.n_src = n_src, a.rows_per_batch = rows_per_batch, a.K = K, a.Cout = Cout, a.ldu = ldu, a.ldv = ldv;
+  a.ldy = ldy, a.ycol0 = ycol0, a.ycols = ycols, a.win0_col0 = win0_col0, a.win0_cols = win0_cols;
+  a.win1_col0 = win1_col0, a.win1_cols = win1_cols, a.partial_tpb = partial_tpb, a.ldyd = ldyd;
+  a.required = a.aligned = a.Yd_aligned = true;
+  a.counts = a.V0 = flags & PDR_GATHER_HAS_COUNTS;
+  a.s1 = a.r1 = flags & PDR_GATHER_HAS_S1;
+  a.s2 = a.r2 = flags & PDR_GATHER_HAS_S2;
+  a.Y = flags & PDR_GATHER_HAS_Y, a.partial = flags & PDR_GATHER_HAS_PARTIAL;
+  a.tile_valid = flags & PDR_GATHER_HAS_TILES;
+  a.idx0 = a.Yd = a.wrow0 = flags & PDR_GATHER_HAS_TWIN;
+  GatherPlan p;
+  const int rc = plan_gather(a, &p);
+  const int v[24] = {p.lpr, p.kpow2, p.has_s, p.has_em, p.ywin, p.stats, p.shared, p.shared_rows, p.mw.c0a, p.mw.na,
+                     p.mw.c0b, p.mw.nb, p.w4, p.passes, p.grid_x, p.grid_y, p.n_main, p.n_twin, p.tpb, p.twin_tpb,
+                     p.ycol0, p.y4, p.tiles, 0};
+  for (int i = 0; i < 24; ++i) out[i] = rc == PDR_OK ? v[i] : 0;
+  return rc;
 }
 
 extern "C" int pdr_gather_moments(const float* U, int ldu, int n_src, const float* V, const float* V0, int ldv,
@@ -789,7 +890,7 @@ extern "C" int pdr_gather_moments_tiles(const float* U, int ldu, int n_src, cons
                                         float* partial, int relu_col0, int win0_col0, int win0_cols, int win1_col0,
                                         int win1_cols, const unsigned char* tile_valid, int partial_tpb,
                                         pdr_stream_t stream) {
-  if (!tile_valid || partial_tpb < (rows_per_batch + 127) / 128) return PDR_EINVAL;
+  if (!tile_valid) return PDR_EINVAL;
   return gather_launch(U, ldu, n_src, V, V0, ldv, idx, counts, s1, r1, s2, r2, B, rows_per_batch, K, Cout, nullptr, 0,
                        partial, relu_col0, 0, -1, win0_col0, win0_cols, win1_col0, win1_cols, tile_valid, partial_tpb,
                        stream);
@@ -801,7 +902,7 @@ extern "C" int pdr_gather_moments_tiles_twin(const float* U, int ldu, int n_src,
                                              int win0_cols, int win1_col0, int win1_cols,
                                              const unsigned char* tile_valid, int partial_tpb, const int* idx0,
                                              float* Yd, int ldyd, const int* wrow0, float wmul, pdr_stream_t stream) {
-  if (!tile_valid || !idx0 || rows_per_batch <= 0 || K <= 0 || rows_per_batch % K != 0) return PDR_EINVAL;
+  if (!tile_valid || !idx0) return PDR_EINVAL;
   return gather_launch(U, ldu, n_src, V, V0, ldv, idx, counts, nullptr, nullptr, nullptr, nullptr, B, rows_per_batch, K,
                        Cout, nullptr, 0, partial, relu_col0, 0, -1, win0_col0, win0_cols, win1_col0, win1_cols, tile_valid,
                        partial_tpb, stream, idx0, Yd, ldyd, wrow0, wmul);
@@ -825,7 +926,7 @@ extern "C" int pdr_gather_add_tiles(const float* U, int ldu, int n_src, const fl
                                     int rows_per_batch, int K, int Cout, float* Y, int ldy, float* partial,
                                     int relu_col0, int ycol0, int ycols, const unsigned char* tile_valid,
                                     int partial_tpb, pdr_stream_t stream) {
-  if (!tile_valid || partial_tpb < (rows_per_batch + 127) / 128) return PDR_EINVAL;
+  if (!tile_valid) return PDR_EINVAL;
   return gather_launch(U, ldu, n_src, V, V0, ldv, idx, counts, s1, r1, s2, r2, B, rows_per_batch, K, Cout, Y, ldy, partial,
                        relu_col0, ycol0, ycols, 0, Cout, 0, 0, tile_valid, partial_tpb, stream);
 }
@@ -839,7 +940,7 @@ extern "C" int pdr_gather_add_tiles_twin(const float* U, int ldu, int n_src, con
                                          int Cout, float* Y, int ldy, float* partial, int relu_col0, int ycol0,
                                          int ycols, const unsigned char* tile_valid, int partial_tpb, const int* idx0,
                                          float* Yd, int ldyd, const int* wrow0, float wmul, pdr_stream_t stream) {
-  if (!tile_valid || !idx0 || rows_per_batch <= 0 || K <= 0 || rows_per_batch % K != 0) return PDR_EINVAL;
+  if (!tile_valid || !idx0) return PDR_EINVAL;
   return gather_launch(U, ldu, n_src, V, V0, ldv, idx, counts, nullptr, nullptr, nullptr, nullptr, B, rows_per_batch, K,
                        Cout, Y, ldy, partial, relu_col0, ycol0, ycols, 0, Cout, 0, 0, tile_valid, partial_tpb, stream, idx0,
                        Yd, ldyd, wrow0, wmul);
