@@ -63,7 +63,7 @@ typedef void *pdr_stream_t; /* hipStream_t */
  *                pdr_emd_cost_ragged / pdr_matchcost_ragged / pdr_matchcost_grad_ragged are new; pdr_emd_cost_grad /
  *                pdr_emd_cost_grad_ragged are new; pdr_chamfer_pairwise is new; pdr_fps_plan / pdr_knn_plan /
  *                pdr_ball_query_plan (host-only dispatch queries) are new; pdr_gather_plan (the same for
- *                pdr_gather_add* / pdr_gather_moments*) is new. */
+ *                pdr_gather_add* / pdr_gather_moments*) is new; pdr_occupancy_grid is new. */
 int pdr_version(void);
 /* last hip error string seen by this thread after a PDR_ELAUNCH ("" if none) */
 const char *pdr_last_error(void);
@@ -224,6 +224,37 @@ int pdr_chamfer_nn_ragged(const float *x, const float *y, const int64_t *lengths
  *     pairs: PDR_EUNSUPPORTED.  cd and the clouds are indexed in size_t. */
 int pdr_chamfer_pairwise(const float *x, const float *y, const int64_t *lengths_x, const int64_t *lengths_y,
                          int S, int R, int n, int m, int symmetric, float *cd, pdr_stream_t stream);
+/* Voxel-grid occupancy counters of a SET of clouds (the loop of entropy_of_occupancy_grid,
+ * pointnet2/models/pvd/metrics/evaluation_metrics.py:198-237, which queries a KD-tree per cloud and counts in Python):
+ *     clouds (S,n,3) f32  ->  counters[c] += points of all clouds whose nearest kept grid cell is c,
+ *                             bernoulli[c] += clouds with at least one such point        (cells int32 each)
+ * The call ADDS: the caller zero-initialises both arrays, so a set can be fed in chunks.  ONE launch (a workgroup per
+ * cloud, its per-cell counts in LDS, then one integer atomic add per occupied cell and array), no workspace, no
+ * allocation, no synchronisation, no floating-point atomics: the outputs are deterministic, and the call is capturable.
+ *   - the grid is DATA built by the caller as the reference builds it (unit_cube_grid_point_cloud :163-181):
+ *     axis[i] = (float)(i * spacing - 0.5), spacing = 1.0 / (R - 1) in double, R values; cell (i,j,k) has the linear
+ *     index (i R + j) R + k and cell_of[linear] (R^3 int32) is its compact index in [0, cells) -- the kept cells
+ *     numbered in ascending linear order -- or -1 for a cell that was clipped away.  All three in DEVICE memory.  An
+ *     entry outside [0, cells) is treated as -1.
+ *   - the nearest-cell rule.  The point is widened to double.  Per axis the index i with the smallest |axis[i] - p|
+ *     (axis[i] widened, compared in double) is taken; the lower index wins a tie and a point beyond the ends clamps.
+ *     If cell_of keeps that cell it is the answer; otherwise the answer is the kept cell with the smallest
+ *     (dx dx + dy dy) + dz dz in double on the widened differences (no fused multiply-add).
+ *     equal distances: the lowest compact index.  (sklearn's NearestNeighbors, which the reference queries, pins no
+ *     order among EXACTLY tied cells: this order is the builder's contract, not a pin, as for pdr_knn_points.  On
+ *     tie-free input -- the two nearest kept cells more than 1e-12 apart in squared distance -- the counters are
+ *     identical to the reference's: tests/golden/make_jsd_golden.py asserts it.)
+ *   - lengths follows pdr_chamfer_pairwise: int64 array of S entries in DEVICE memory, clamped on the device to [0, n],
+ *     NULL = every cloud is full, n stays the row stride; rows at or beyond a length are never read for their value.
+ *   - a point with a non-finite coordinate inside its length goes to no cell and adds 1 to skipped[0] (device int32,
+ *     may be NULL); nothing is indexed with a value derived from it.  (So does every point when cell_of keeps no
+ *     cell at all.)
+ *   - validation, decided on the host before any launch: a negative size, n <= 0 with S > 0, cells <= 0 or a NULL
+ *     clouds / axis / cell_of / counters / bernoulli: PDR_EINVAL; S == 0: PDR_OK, nothing launched, no pointer looked
+ *     at; R outside [2, 32], cells > R^3 or S n >= 2^31: PDR_EUNSUPPORTED. */
+int pdr_occupancy_grid(const float *clouds, const int64_t *lengths, int S, int n, int R,
+                       const float *axis, const int32_t *cell_of, int cells,
+                       int32_t *counters, int32_t *bernoulli, int32_t *skipped, pdr_stream_t stream);
 /* pdr_knn_points for group_knn (pointnet2_utils.py:487-514) inside the fused network: same search, int32 indices
  * and the normalised interpolation weights w = (1/(d2+1e-8)) / sum_k (1/(d2_k+1e-8)) of :500-503 (SQUARED
  * distances, k ascending) in the same pass.  Requires K <= min(n2, 16). */

@@ -266,6 +266,40 @@ def chamfer_pairwise(x, y, x_lengths=None, y_lengths=None, symmetric=False):
     return cd
 
 
+def occupancy_grid(clouds, axis, cell_of, cells, lengths=None, out=None):
+    """Occupancy counters of a set of clouds on a voxel grid in one launch (pdr_occupancy_grid): clouds (S,n,3) f32,
+    axis (R,) f32 and cell_of (R,R,R) i32 -- the grid tables of set_metrics.grid_tables, on the clouds' device --
+    -> (counters (cells,) i32, bernoulli (cells,) i32, skipped (1,) i32).  The kernel ADDS: `out` is such a triple to
+    accumulate into (nothing is allocated then); without it the three are allocated as zeros.  `lengths` (S,) int64:
+    cloud s is clouds[s, :lengths[s]]."""
+    _req(clouds, "clouds", torch.float32)
+    _req_xyz(clouds, "clouds")
+    _req(axis, "axis", torch.float32)
+    _req(cell_of, "cell_of", torch.int32)
+    _same_device(clouds, axis, cell_of)
+    _req_lengths(lengths, "lengths", clouds)
+    R, cells = int(axis.numel()), int(cells)
+    if cell_of.numel() != R ** 3:
+        raise RuntimeError("cell_of must hold R^3 = %d entries, got %d" % (R ** 3, cell_of.numel()))
+    if out is None:
+        counters, bernoulli, skipped = (torch.zeros((k,), dtype=torch.int32, device=clouds.device)
+                                        for k in (max(cells, 0), max(cells, 0), 1))
+    else:
+        counters, bernoulli, skipped = out
+        for t, name, k in ((counters, "counters", cells), (bernoulli, "bernoulli", cells), (skipped, "skipped", 1)):
+            _req(t, name, torch.int32)
+            if t.numel() != k:
+                raise RuntimeError("%s must hold %d entries, got %d" % (name, k, t.numel()))
+        _same_device(clouds, counters, bernoulli, skipped)
+    S, n, _ = clouds.shape
+    with torch.cuda.device(clouds.device):
+        _lib.check(_lib.load().pdr_occupancy_grid(clouds.data_ptr(), _ptr(lengths), S, n, R, axis.data_ptr(),
+                                                  cell_of.data_ptr(), cells, counters.data_ptr(),
+                                                  bernoulli.data_ptr(), skipped.data_ptr(), _stream()),
+                   "occupancy_grid")
+    return counters, bernoulli, skipped
+
+
 def knn_group(x, y, K):
     """knn_points for group_knn in the fused network: (dists (B,n1,K) f32, idx (B,n1,K) i32, weights (B,n1,K) f32)
     with weights = normalised 1 / (d2 + 1e-8) (pointnet2_utils.py:500-503)."""
