@@ -63,7 +63,8 @@ typedef void *pdr_stream_t; /* hipStream_t */
  *                pdr_emd_cost_ragged / pdr_matchcost_ragged / pdr_matchcost_grad_ragged are new; pdr_emd_cost_grad /
  *                pdr_emd_cost_grad_ragged are new; pdr_chamfer_pairwise is new; pdr_fps_plan / pdr_knn_plan /
  *                pdr_ball_query_plan (host-only dispatch queries) are new; pdr_gather_plan (the same for
- *                pdr_gather_add* / pdr_gather_moments*) is new; pdr_occupancy_grid is new. */
+ *                pdr_gather_add* / pdr_gather_moments*) is new; pdr_occupancy_grid is new; pdr_fused_layer_pool_plan (the same
+ *                for the two pooled entry points) is new. */
 int pdr_version(void);
 /* last hip error string seen by this thread after a PDR_ELAUNCH ("" if none) */
 const char *pdr_last_error(void);
@@ -482,7 +483,8 @@ int pdr_fused_layer_plan(const pdr_layer_in_t *in, long P, int Cin, const float 
 /* Y (P,Cout; ld ldy) = prologue(X) . Wt + bias, Wt (Cin,Cout) row-major (the conv weight
  * transposed; 16-B aligned, leading dimension ldw >= Cout with ldw % 4 == 0), exact fp32 MFMA.
  * Sources whose pointers are 16-B aligned and whose leading dimensions are multiples of 4 floats
- * (rows padded to a multiple of 4 channels) are staged with 16-B loads.  partial: NULL or (B*tiles_per_batch, Cout, 2) floats receiving the
+ * (rows padded to a multiple of 4 channels) are staged with 16-B loads; what the padding columns hold is never used
+ * (they may be uninitialised, NaN included: channels beyond a segment's C enter the product as exact zeros).  partial: NULL or (B*tiles_per_batch, Cout, 2) floats receiving the
  * per-tile sum / sum of squares of y (columns >= relu_col0: of relu(y)). */
 int pdr_fused_layer(const pdr_layer_in_t *in, long P, int Cin, const float *Wt, int ldw,
                     const float *bias, int Cout, float *Y, int ldy, float *partial,
@@ -533,6 +535,21 @@ int pdr_fused_layer_pool_f16x3(const pdr_layer_in_t *in, long P, int Cin, const 
                                const float *bias, int D, const float *values, int ldv,
                                const float *vscale, const float *vshift, int v_relu, const int *counts,
                                int K, float *out, int ldo, pdr_stream_t stream);
+/* The launch a pooled entry point would make for these arguments, without launching (host only; nothing behind the
+ * pointers is read): split = 0 asks for pdr_fused_layer_pool (W = Wt, ldw_or_nchunks = ldw), split != 0 for
+ * pdr_fused_layer_pool_f16x3 (W = Wp, ldw_or_nchunks = nchunks).  Returns exactly the code that entry point returns for
+ * the same `in`, P, Cin, weights, D, values, ldv, K, out and ldo (bias, vscale, vshift, v_relu, counts and the stream
+ * decide nothing); PDR_EINVAL also when `plan` is NULL.  On PDR_OK plan[0..7] (8 ints) =
+ *   {wave-specialised kernel (csrc/fused_layer_ws.hip; 0 = the uniform-wave kernel's pooled epilogue)?,
+ *    tile variant id (pdr_fused_layer_variant(rows_per_batch, D)), split-f16 arithmetic?,
+ *    row tiles of the launch = P / rows_per_batch * ceil(rows_per_batch / tile rows) (with a tile subset: the tiles the
+ *    list is drawn from), column blocks = ceil(D / tile columns),
+ *    tile subset (in->tile_list)?, row map (in->out_rows)?, patched rows (in->patch_values)?};
+ * `plan` is not written otherwise.  The wave-specialised kernel is taken when PDR_FUSED_WS is not 0, rows_per_batch is a
+ * multiple of the tile rows and the variant has one (not 3, not 6); the last three need it. */
+int pdr_fused_layer_pool_plan(const pdr_layer_in_t *in, long P, int Cin, const void *W, int ldw_or_nchunks,
+                              int D, const float *values, int ldv, int K, const float *out, int ldo,
+                              int split, int *plan);
 /* chan_stats[b, coff+c] (double sum, double sumsq) = mult * sum over tiles of batch b;
  * `partial` points at the first of C columns inside rows of ldp columns */
 int pdr_gn_reduce(const float *partial, int ldp, int B, int tiles_per_batch, int C, double mult,

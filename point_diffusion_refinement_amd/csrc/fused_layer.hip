@@ -105,6 +105,7 @@ __global__ __launch_bounds__(256, 2) void fused_layer_kernel(
   float f_s = 1.0f, f_h = 0.0f, f_a = 0.0f;
   bool f_cok = false;
   int f_kmax = 0;
+  int f_okm = 0;               // VEC: bit j = channel j of this thread's float4 lies inside the segment
 
   for (int tile = blockIdx.x; tile < n_row_tiles; tile += gridDim.x) {
     const int b = tile / tpb, tb = tile - b * tpb;
@@ -143,9 +144,11 @@ __global__ __launch_bounds__(256, 2) void fused_layer_kernel(
         const int cl = ks + 4 * vc4;                                 // first channel of this float4
         const int clc = min(cl, ((seg.C + 3) & ~3) - 4);             // keep the 16-B load in the row
         f_cok = cl == clc;                                           // else: all 4 lanes are padding
+        f_okm = 0;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
           const bool ok = f_cok && (clc + j) < seg.C;
+          f_okm |= ok ? 1 << j : 0;
           const int cg = cbase + min(clc + j, seg.C - 1);
           // channels beyond the segment are forced to 0 (scale = shift = add = 0)
           ps[j] = ok ? (sc_b ? sc_b[cg] : 1.0f) : 0.0f;
@@ -255,7 +258,8 @@ __global__ __launch_bounds__(256, 2) void fused_layer_kernel(
             v = __builtin_fmaf(v, ps[j], ph[j]);
             v = fmaxf(v, lo_post) + pa[j];
             if constexpr (RADD) v = __builtin_fmaf(q[j], pok[j], v);
-            As[4 * vc4 + j][vr0 + VSTEP * i] = v;
+            // a padding column may hold anything (NaN x 0 is NaN): the channels beyond the segment are exactly 0
+            As[4 * vc4 + j][vr0 + VSTEP * i] = (f_okm >> j & 1) ? v : 0.0f;
           }
         }
       } else {
@@ -972,7 +976,59 @@ int plan_pool(const pdr_layer_in_t* in, long P, int Cin, bool weights_ok, int D,
   pp->ncol = (D + pdr::tile_tn(pp->id) - 1) / pdr::tile_tn(pp->id);
   return PDR_OK;
 }
+
+// The dispatch decision of the two pooled entry points: decide_pool() is the only place that decides or refuses;
+// pdr_fused_layer_pool / pdr_fused_layer_pool_f16x3 launch what it names, pdr_fused_layer_pool_plan reports it.
+// W / ldw_or_nchunks: Wt and ldw of the exact entry point, Wp and nchunks of the split one.
+struct PoolDecision {
+  PoolPlan pp;
+  bool ws;            // fused_layer_ws_kernel (else fused_layer_kernel<.., POOL = true>)
+  LayerSource src;
+};
+int decide_pool(const pdr_layer_in_t* in, long P, int Cin, const void* W, int ldw_or_nchunks, int D,
+                const float* values, int ldv, int K, const float* out, int ldo, bool split, PoolDecision* d) {
+  const bool w16 = W && reinterpret_cast<uintptr_t>(W) % 16 == 0;
+  const bool weights_ok = split ? w16 && ldw_or_nchunks > 0 : w16 && ldw_or_nchunks >= D && ldw_or_nchunks % 4 == 0;
+  PoolPlan& pp = d->pp;
+  const int rc = plan_pool(in, P, Cin, weights_ok, D, values, ldv, K, out, ldo, &pp);
+  if (rc != PDR_OK) return rc;
+  if (split) {
+    if (pp.nch != ldw_or_nchunks) return PDR_EINVAL;   // the image was packed for another segment structure
+    if (!pp.vec || !use_ws_kernels()) return PDR_EUNSUPPORTED;
+    if (!pdr::tile_has_split(pp.id) || in->rows_per_batch % pp.tm != 0) return PDR_EUNSUPPORTED;
+  } else if (!pp.vec) {
+    return PDR_EUNSUPPORTED;
+  }
+  if (in->tile_list && (!in->n_tiles || pp.tm != 128)) return PDR_EUNSUPPORTED;
+  d->src = pdr::layer_source(*in);
+  // wave-specialised kernels carry the pooled epilogue for the tile shapes whose rows tile whole queries
+  d->ws = use_ws_kernels() && in->rows_per_batch % pp.tm == 0 && pdr::fused_layer_ws_supported(pp.id, d->src, *in, Cin);
+  if (split && !d->ws) return PDR_EUNSUPPORTED;
+  // tile subsets / row maps / patched rows: wave-specialised kernels only
+  if (!d->ws && (in->tile_list || in->out_rows || in->patch_values)) return PDR_EUNSUPPORTED;
+  return PDR_OK;
+}
 }  // namespace
+
+// plan[0..7] = {wave-specialised kernel?, tile variant id, split-f16 arithmetic?, row tiles, column blocks, tile
+// subset?, row map?, patched rows?} of the launch the matching pooled entry point would make, and its return code.
+extern "C" int pdr_fused_layer_pool_plan(const pdr_layer_in_t* in, long P, int Cin, const void* W, int ldw_or_nchunks,
+                                         int D, const float* values, int ldv, int K, const float* out, int ldo,
+                                         int split, int* plan) {
+  if (!plan) return PDR_EINVAL;
+  PoolDecision d;
+  const int rc = decide_pool(in, P, Cin, W, ldw_or_nchunks, D, values, ldv, K, out, ldo, split != 0, &d);
+  if (rc != PDR_OK) return rc;
+  plan[0] = d.ws;
+  plan[1] = d.pp.id;
+  plan[2] = split != 0;
+  plan[3] = static_cast<int>(d.pp.ntiles);
+  plan[4] = d.pp.ncol;
+  plan[5] = in->tile_list != nullptr;
+  plan[6] = in->out_rows != nullptr;
+  plan[7] = in->patch_values != nullptr;
+  return PDR_OK;
+}
 
 // pdr_fused_layer_pool with the score conv on split-f16 arithmetic (packed weight image as pdr_fused_layer_f16x3);
 // the wave-specialised tiles of pdr::tile_has_split only: PDR_EUNSUPPORTED otherwise (the caller uses the exact entry
@@ -981,19 +1037,12 @@ extern "C" int pdr_fused_layer_pool_f16x3(const pdr_layer_in_t* in, long P, int 
                                           const float* bias, int D, const float* values, int ldv,
                                           const float* vscale, const float* vshift, int v_relu,
                                           const int* counts, int K, float* out, int ldo, pdr_stream_t stream) {
-  PoolPlan pp;
-  const int rc = plan_pool(in, P, Cin, Wp && nchunks > 0 && reinterpret_cast<uintptr_t>(Wp) % 16 == 0, D, values, ldv,
-                           K, out, ldo, &pp);
+  PoolDecision d;
+  const int rc = decide_pool(in, P, Cin, Wp, nchunks, D, values, ldv, K, out, ldo, true, &d);
   if (rc != PDR_OK) return rc;
-  if (pp.nch != nchunks) return PDR_EINVAL;   // the image was packed for another segment structure
-  if (!pp.vec || !use_ws_kernels()) return PDR_EUNSUPPORTED;
-  if (!pdr::tile_has_split(pp.id) || in->rows_per_batch % pp.tm != 0) return PDR_EUNSUPPORTED;
-  if (in->tile_list && (!in->n_tiles || pp.tm != 128)) return PDR_EUNSUPPORTED;
-  const LayerSource src = pdr::layer_source(*in);
-  if (!pdr::fused_layer_ws_supported(pp.id, src, *in, Cin)) return PDR_EUNSUPPORTED;
   const PoolArgs pa{values, vscale, vshift, counts, out, ldv, ldo, K, v_relu};
-  pdr::launch_fused_layer_ws(pp.id, src, *in, Cin, reinterpret_cast<const float*>(Wp), nchunks, bias, D, nullptr, 0,
-                             nullptr, D, static_cast<int>(pp.ntiles), pp.ncol, pdr::as_stream(stream), true, &pa);
+  pdr::launch_fused_layer_ws(d.pp.id, d.src, *in, Cin, reinterpret_cast<const float*>(Wp), nchunks, bias, D, nullptr, 0,
+                             nullptr, D, static_cast<int>(d.pp.ntiles), d.pp.ncol, pdr::as_stream(stream), true, &pa);
   return pdr::check_launch();
 }
 
@@ -1002,24 +1051,18 @@ extern "C" int pdr_fused_layer_pool(const pdr_layer_in_t* in, long P, int Cin, c
                                     const float* vscale, const float* vshift, int v_relu,
                                     const int* counts, int K, float* out, int ldo,
                                     pdr_stream_t stream) {
-  PoolPlan pp;
-  const int rc = plan_pool(in, P, Cin, Wt && ldw >= D && ldw % 4 == 0 && reinterpret_cast<uintptr_t>(Wt) % 16 == 0, D,
-                           values, ldv, K, out, ldo, &pp);
+  PoolDecision d;
+  const int rc = decide_pool(in, P, Cin, Wt, ldw, D, values, ldv, K, out, ldo, false, &d);
   if (rc != PDR_OK) return rc;
-  if (!pp.vec) return PDR_EUNSUPPORTED;
-  if (in->tile_list && (!in->n_tiles || pp.tm != 128)) return PDR_EUNSUPPORTED;
+  const PoolPlan& pp = d.pp;
   hipStream_t s = pdr::as_stream(stream);
   const PoolArgs pa{values, vscale, vshift, counts, out, ldv, ldo, K, v_relu};
   const int nt = static_cast<int>(pp.ntiles);
-  // wave-specialised kernels carry the pooled epilogue for the tile shapes whose rows tile whole queries
-  const LayerSource src = pdr::layer_source(*in);
-  if (use_ws_kernels() && in->rows_per_batch % pp.tm == 0 && pdr::fused_layer_ws_supported(pp.id, src, *in, Cin)) {
-    pdr::launch_fused_layer_ws(pp.id, src, *in, Cin, Wt, ldw, bias, D, nullptr, 0, nullptr, D, nt, pp.ncol, s, false,
+  if (d.ws) {
+    pdr::launch_fused_layer_ws(pp.id, d.src, *in, Cin, Wt, ldw, bias, D, nullptr, 0, nullptr, D, nt, pp.ncol, s, false,
                                &pa);
     return pdr::check_launch();
   }
-  // tile subsets / row maps / patched rows: wave-specialised kernels only
-  if (in->tile_list || in->out_rows || in->patch_values) return PDR_EUNSUPPORTED;
   const LayerArgs a{s, *in, Cin, Wt, ldw, bias, D, nullptr, 0, nullptr, D, nt, pa};
   pdr::with_tile(pp.id, [&](auto t) { launch_k<decltype(t), false, true, false, true>(uniform_grid(pp.ntiles, pp.ncol), a); });
   return pdr::check_launch();
