@@ -64,7 +64,8 @@ typedef void *pdr_stream_t; /* hipStream_t */
  *                pdr_emd_cost_grad_ragged are new; pdr_chamfer_pairwise is new; pdr_fps_plan / pdr_knn_plan /
  *                pdr_ball_query_plan (host-only dispatch queries) are new; pdr_gather_plan (the same for
  *                pdr_gather_add* / pdr_gather_moments*) is new; pdr_occupancy_grid is new; pdr_fused_layer_pool_plan (the same
- *                for the two pooled entry points) is new. */
+ *                for the two pooled entry points) is new; pdr_scatter_workspace_bytes and the four deterministic backward
+ *                twins pdr_*_grad_det are new. */
 int pdr_version(void);
 /* last hip error string seen by this thread after a PDR_ELAUNCH ("" if none) */
 const char *pdr_last_error(void);
@@ -275,12 +276,56 @@ int pdr_knn_plan(int B, int n1, int n2, int K, int has_nn, int group, int out[4]
  * K = 1 cross-check: chamfer3D.cu:155-195):
  *   grad_x[p] = sum_k 2 g[p,k] (x[p] - y[idx[p,k]]),  grad_y[j] = -sum_{idx[p,k] = j} (same term).
  * idx < 0 (padding) is skipped.  grad_x (B,n1,3) is overwritten; grad_y (B,n2,3) is zeroed on the
- * stream and accumulated with float atomics (summation order not fixed).
+ * stream and accumulated with float atomics (summation order not fixed; pdr_knn_points_grad_det below fixes it).
  * This skip is also what makes pdr_knn_points_ragged differentiable without a kernel of its own: its padded queries
  * and the slots beyond a cloud's length carry idx -1, so padded rows of either cloud receive exactly zero. */
 int pdr_knn_points_grad(const float *x, const float *y, const int64_t *idx,
                         const float *grad_dists, int B, int n1, int n2, int K,
                         float *grad_x, float *grad_y, pdr_stream_t stream);
+
+/* ---- deterministic backward twins -------------------------------------------
+ * pdr_gather_points_grad, pdr_group_points_grad, pdr_three_interpolate_grad and the grad_y half of pdr_knn_points_grad
+ * scatter with float atomics: the same gradient, but the order of the fp32 adds -- and with it the last bits -- changes
+ * from run to run.  The _det calls below take the same arguments plus a workspace and compute the same sums in ONE
+ * FIXED ORDER, so the same input gives the same bits; the atomic calls and their outputs are unchanged.
+ *   - the summation order.  Every output element starts from +0.0f and its contributions are added one after the
+ *     other in fp32, in ascending order of their SOURCE POSITION in the index array; every product is rounded before it
+ *     is added (no fused multiply-add):
+ *         gather / group   grad_points[b,c,d]  = sum over pos with idx[b,pos] == d, pos ascending, of grad_out[b,c,pos]
+ *                          (pos = j for gather, j ns + k for group)
+ *         interpolate      grad_points[b,c,d]  = sum over pos = 3 j + t with idx[b,j,t] == d, pos ascending, of
+ *                          fl(grad_out[b,c,j] * weight[b,j,t])
+ *         kNN grad_y       grad_y[b,d,c] = 0 - d_1 - d_2 - ... over pos = j K + t with idx[b,j,t] == d, pos ascending,
+ *                          d_i = fl(fl(2 grad_dists[b,j,t]) * fl(x[b,j,c] - y[b,d,c])); idx < 0 is skipped
+ *         kNN grad_x       as pdr_knn_points_grad (t ascending in registers: already order-fixed), the same bits
+ *     This is the order of the sequential loops of oracle/pdr_oracle.c, whose results these calls reproduce bit for bit.
+ *     A destination that no source names gets +0.0f.  Every output element is written exactly once.
+ *   - how.  An inverse index (per destination, its source positions ascending) is built in the workspace by a stable
+ *     counting sort -- integer atomics count, nothing floating-point is atomic --, then one thread per (destination,
+ *     8-channel slab) adds its list; a list of 256 or more sources (a ball query without a hit names point 0 in every
+ *     slot) is added by one wave, lane = channel, still one add after the other.  Five launches and one memset of a part
+ *     of the workspace on `stream` (kNN: six launches), no allocation, no synchronisation: capturable.
+ *   - P, the source positions per cloud, is m, np ns, 3 n and n1 K; N, the destinations, is N, N, m and n2.
+ *     pdr_scatter_workspace_bytes(B, P, N) is the size of the workspace of such a call: positive for positive sizes,
+ *     non-decreasing in each argument over the supported sizes, 0 for B <= 0 and for sizes the calls refuse.  Its contents are private and
+ *     undefined afterwards; two calls in flight at once need a workspace each.
+ *   - validation, decided on the host before any launch, in this order: the atomic twin's size checks and its empty
+ *     cases with the twin's codes (B == 0: PDR_OK, nothing looked at); sizes these kernels do not index --
+ *     N > 16384, P > 4194304, B > 65535 or B P >= 2^31 --: PDR_EUNSUPPORTED; then the twin's pointer checks, and with
+ *     sources to add (P > 0; kNN: also n2 > 0) a NULL workspace, or one that is not 4-byte aligned: PDR_EINVAL.
+ *     With P == 0 the output is zero-filled and the workspace is not looked at.
+ *   - an index outside [0, N) is skipped (the kNN padding -1 by contract; any other such value is still an error of
+ *     the caller, but it reaches no memory here). */
+size_t pdr_scatter_workspace_bytes(int B, int P, int N);
+int pdr_gather_points_grad_det(const float *grad_out, const int *idx, int B, int C, int N, int m,
+                               float *grad_points, void *workspace, pdr_stream_t stream);
+int pdr_group_points_grad_det(const float *grad_out, const int *idx, int B, int C, int N, int np, int ns,
+                              float *grad_points, void *workspace, pdr_stream_t stream);
+int pdr_three_interpolate_grad_det(const float *grad_out, const int *idx, const float *weight, int B, int C,
+                                   int n, int m, float *grad_points, void *workspace, pdr_stream_t stream);
+int pdr_knn_points_grad_det(const float *x, const float *y, const int64_t *idx, const float *grad_dists,
+                            int B, int n1, int n2, int K, float *grad_x, float *grad_y, void *workspace,
+                            pdr_stream_t stream);
 
 /* ---- approximate EMD --------------------------------------------------------
  * approxmatch_forward(xyz1 (B,n,3), xyz2 (B,m,3)) -> match (B,m,n)

@@ -45,6 +45,11 @@ SIGNATURES = {
     "pdr_knn_group": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
     "pdr_knn_plan": (_I, [_I, _I, _I, _I, _I, _I, _P]),
     "pdr_knn_points_grad": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
+    "pdr_scatter_workspace_bytes": (_Z, [_I, _I, _I]),
+    "pdr_gather_points_grad_det": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P]),
+    "pdr_group_points_grad_det": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
+    "pdr_three_interpolate_grad_det": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
+    "pdr_knn_points_grad_det": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
     "pdr_emd_workspace_bytes": (_Z, [_I, _I, _I]),
     "pdr_matchcost_workspace_bytes": (_Z, [_I, _I, _I]),
     "pdr_approxmatch": (_I, [_P, _P, _I, _I, _I, _P, _P, _P]),

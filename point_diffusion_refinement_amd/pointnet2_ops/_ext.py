@@ -42,6 +42,34 @@ def _same_device(*ts):
             raise RuntimeError("all tensors must live on the same device")
 
 
+_deterministic = None      # set_deterministic: None = follow torch.are_deterministic_algorithms_enabled()
+
+
+def set_deterministic(mode):
+    """Choose the backward kernels of gather / group / three_interpolate / knn_points: True = the order-fixed
+    `*_grad_det` calls (same input, same bits), False = the atomic ones, None (the default) = follow
+    `torch.are_deterministic_algorithms_enabled()`.  Returns the previous setting.  In deterministic mode a size the
+    deterministic kernels do not support raises; nothing falls back to atomics."""
+    global _deterministic
+    if mode is not None and not isinstance(mode, bool):
+        raise TypeError("set_deterministic takes True, False or None, got %r" % (mode,))
+    prev, _deterministic = _deterministic, mode
+    return prev
+
+
+def is_deterministic():
+    """Whether the autograd Functions take the deterministic backward kernels right now."""
+    if _deterministic is None:
+        return bool(torch.are_deterministic_algorithms_enabled())
+    return _deterministic
+
+
+def _scatter_workspace(B, P, N, device):
+    """Scratch of one `*_grad_det` call (pdr_scatter_workspace_bytes), a torch allocation per call."""
+    nbytes = _lib.load().pdr_scatter_workspace_bytes(int(B), int(P), int(N))
+    return torch.empty((max(int(nbytes), 4),), dtype=torch.uint8, device=device)
+
+
 def furthest_point_sampling(points, nsamples):
     """(B,N,3) f32 -> (B,nsamples) i32   [sampling.cpp:66-87]"""
     _req(points, "points", torch.float32)
@@ -82,6 +110,22 @@ def gather_points_grad(grad_out, idx, n):
     with torch.cuda.device(grad_out.device):
         _lib.check(_lib.load().pdr_gather_points_grad(grad_out.data_ptr(), idx.data_ptr(), B, C, int(n), m,
                                                       out.data_ptr(), _stream()), "gather_points_grad")
+    return out
+
+
+def gather_points_grad_det(grad_out, idx, n):
+    """gather_points_grad with a fixed summation order (pdr_gather_points_grad_det): sources added in ascending
+    position from +0.0, the same bits run after run."""
+    _req(grad_out, "grad_out", torch.float32)
+    _req(idx, "idx", torch.int32)
+    _same_device(grad_out, idx)
+    B, C, m = grad_out.shape
+    out = torch.empty((B, C, n), dtype=torch.float32, device=grad_out.device)
+    ws = _scatter_workspace(B, m, n, grad_out.device)
+    with torch.cuda.device(grad_out.device):
+        _lib.check(_lib.load().pdr_gather_points_grad_det(grad_out.data_ptr(), idx.data_ptr(), B, C, int(n), m,
+                                                          out.data_ptr(), ws.data_ptr(), _stream()),
+                   "gather_points_grad_det")
     return out
 
 
@@ -132,6 +176,21 @@ def group_points_grad(grad_out, idx, n):
     return out
 
 
+def group_points_grad_det(grad_out, idx, n):
+    """group_points_grad with a fixed summation order (pdr_group_points_grad_det)."""
+    _req(grad_out, "grad_out", torch.float32)
+    _req(idx, "idx", torch.int32)
+    _same_device(grad_out, idx)
+    B, C, npnt, ns = grad_out.shape
+    out = torch.empty((B, C, n), dtype=torch.float32, device=grad_out.device)
+    ws = _scatter_workspace(B, npnt * ns, n, grad_out.device)
+    with torch.cuda.device(grad_out.device):
+        _lib.check(_lib.load().pdr_group_points_grad_det(grad_out.data_ptr(), idx.data_ptr(), B, C, int(n), npnt, ns,
+                                                         out.data_ptr(), ws.data_ptr(), _stream()),
+                   "group_points_grad_det")
+    return out
+
+
 def three_nn(unknowns, knows):
     """(B,n,3), (B,m,3) -> [dist2 (B,n,3) f32 SQUARED, idx (B,n,3) i32]   [interpolate.cpp:14-40]"""
     _req(unknowns, "unknowns", torch.float32)
@@ -177,6 +236,48 @@ def three_interpolate_grad(grad_out, idx, weight, m):
                                                           C, n, int(m), out.data_ptr(), _stream()),
                    "three_interpolate_grad")
     return out
+
+
+def three_interpolate_grad_det(grad_out, idx, weight, m):
+    """three_interpolate_grad with a fixed summation order (pdr_three_interpolate_grad_det)."""
+    _req(grad_out, "grad_out", torch.float32)
+    _req(idx, "idx", torch.int32)
+    _req(weight, "weight", torch.float32)
+    _same_device(grad_out, idx, weight)
+    B, C, n = grad_out.shape
+    out = torch.empty((B, C, m), dtype=torch.float32, device=grad_out.device)
+    ws = _scatter_workspace(B, 3 * n, m, grad_out.device)
+    with torch.cuda.device(grad_out.device):
+        _lib.check(_lib.load().pdr_three_interpolate_grad_det(grad_out.data_ptr(), idx.data_ptr(), weight.data_ptr(),
+                                                              B, C, n, int(m), out.data_ptr(), ws.data_ptr(),
+                                                              _stream()), "three_interpolate_grad_det")
+    return out
+
+
+def knn_points_grad(p1, p2, idx, grad_dists, deterministic=False):
+    """Backward of knn_points' squared distances: (B,n1,3), (B,n2,3), idx (B,n1,K) i64, grad_dists (B,n1,K)
+    -> (grad_p1, grad_p2).  deterministic=True takes pdr_knn_points_grad_det, whose grad_p2 is summed in a fixed order
+    (grad_p1 is order-fixed in both)."""
+    _req(p1, "p1", torch.float32)
+    _req(p2, "p2", torch.float32)
+    _req(idx, "idx", torch.int64)
+    _req(grad_dists, "grad_dists", torch.float32)
+    _same_device(p1, p2, idx, grad_dists)
+    B, n1, _ = p1.shape
+    n2, K = p2.shape[1], idx.shape[2]
+    g1 = torch.empty_like(p1)
+    g2 = torch.empty_like(p2)
+    lib = _lib.load()
+    with torch.cuda.device(p1.device):
+        if deterministic:
+            ws = _scatter_workspace(B, n1 * K, n2, p1.device)
+            _lib.check(lib.pdr_knn_points_grad_det(p1.data_ptr(), p2.data_ptr(), idx.data_ptr(), grad_dists.data_ptr(),
+                                                   B, n1, n2, K, g1.data_ptr(), g2.data_ptr(), ws.data_ptr(),
+                                                   _stream()), "knn_points_grad_det")
+        else:
+            _lib.check(lib.pdr_knn_points_grad(p1.data_ptr(), p2.data_ptr(), idx.data_ptr(), grad_dists.data_ptr(), B,
+                                               n1, n2, K, g1.data_ptr(), g2.data_ptr(), _stream()), "knn_points_grad")
+    return g1, g2
 
 
 def _req_lengths(t, name, cloud):
@@ -342,15 +443,7 @@ class _KnnDists(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_dists, _grad_idx):
         p1, p2, idx = ctx.saved_tensors
-        B, n1, _ = p1.shape
-        n2, K = p2.shape[1], idx.shape[2]
-        g = grad_dists.contiguous().float()
-        g1 = torch.empty_like(p1)
-        g2 = torch.empty_like(p2)
-        with torch.cuda.device(p1.device):
-            _lib.check(_lib.load().pdr_knn_points_grad(p1.data_ptr(), p2.data_ptr(), idx.data_ptr(), g.data_ptr(), B,
-                                                       n1, n2, K, g1.data_ptr(), g2.data_ptr(), _stream()),
-                       "knn_points_grad")
+        g1, g2 = knn_points_grad(p1, p2, idx, grad_dists.contiguous().float(), deterministic=is_deterministic())
         return g1, g2, None, None, None
 
 

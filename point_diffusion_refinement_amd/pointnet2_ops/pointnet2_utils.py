@@ -9,7 +9,8 @@ the reference's pointnet2_ops/pointnet2_utils.py, running on libpdr_hip.so.
 kNN comes from this package's own `_ext.knn_points` (the reference imports
 pytorch3d.ops.knn, :7).  Autograd: FPS / ball_query / three_nn are
 non-differentiable as in the reference; gather / group / three_interpolate have
-backward kernels.
+backward kernels -- the atomic ones, or, under `_ext.set_deterministic` /
+`torch.use_deterministic_algorithms(True)`, the order-fixed `*_grad_det` ones.
 """
 import torch
 import torch.nn as nn
@@ -59,7 +60,8 @@ class GatherOperation(Function):
     @staticmethod
     def backward(ctx, grad_out):
         (idx,) = ctx.saved_tensors
-        return _ext.gather_points_grad(grad_out.contiguous(), idx, ctx.n), None
+        grad = _ext.gather_points_grad_det if _ext.is_deterministic() else _ext.gather_points_grad
+        return grad(grad_out.contiguous(), idx, ctx.n), None
 
 
 gather_operation = GatherOperation.apply
@@ -91,7 +93,8 @@ class ThreeInterpolate(Function):
     @staticmethod
     def backward(ctx, grad_out):
         idx, weight = ctx.saved_tensors
-        g = _ext.three_interpolate_grad(grad_out.contiguous(), idx, weight, ctx.m)
+        grad = _ext.three_interpolate_grad_det if _ext.is_deterministic() else _ext.three_interpolate_grad
+        g = grad(grad_out.contiguous(), idx, weight, ctx.m)
         return g, torch.zeros_like(idx), torch.zeros_like(weight)
 
 
@@ -108,7 +111,8 @@ class GroupingOperation(Function):
     @staticmethod
     def backward(ctx, grad_out):
         (idx,) = ctx.saved_tensors
-        return _ext.group_points_grad(grad_out.contiguous(), idx, ctx.n), torch.zeros_like(idx)
+        grad = _ext.group_points_grad_det if _ext.is_deterministic() else _ext.group_points_grad
+        return grad(grad_out.contiguous(), idx, ctx.n), torch.zeros_like(idx)
 
 
 grouping_operation = GroupingOperation.apply
