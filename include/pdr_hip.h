@@ -65,7 +65,8 @@ typedef void *pdr_stream_t; /* hipStream_t */
  *                pdr_ball_query_plan (host-only dispatch queries) are new; pdr_gather_plan (the same for
  *                pdr_gather_add* / pdr_gather_moments*) is new; pdr_occupancy_grid is new; pdr_fused_layer_pool_plan (the same
  *                for the two pooled entry points) is new; pdr_scatter_workspace_bytes and the four deterministic backward
- *                twins pdr_*_grad_det are new. */
+ *                twins pdr_*_grad_det are new; pdr_chamfer_loss_workspace_bytes / pdr_chamfer_loss / pdr_chamfer_loss_grad
+ *                are new. */
 int pdr_version(void);
 /* last hip error string seen by this thread after a PDR_ELAUNCH ("" if none) */
 const char *pdr_last_error(void);
@@ -226,6 +227,64 @@ int pdr_chamfer_nn_ragged(const float *x, const float *y, const int64_t *lengths
  *     pairs: PDR_EUNSUPPORTED.  cd and the clouds are indexed in size_t. */
 int pdr_chamfer_pairwise(const float *x, const float *y, const int64_t *lengths_x, const int64_t *lengths_y,
                          int S, int R, int n, int m, int symmetric, float *cd, pdr_stream_t stream);
+/* The Chamfer distance as a TRAINING LOSS (calc_cd(X, refined_X)[loss_idx].mean().backward(), pointnet2/train.py:518):
+ * x (B,n1,3), y (B,n2,3)  ->  sums (B,4) f32, fully written,
+ *     sums[b] = { sum_i d_xy[i], sum_j d_yx[j], sum_i sqrt(d_xy[i]), sum_j sqrt(d_yx[j]) },  d_xy[i] = min_j |x_i - y_j|^2
+ * over the valid points of each cloud (d_yx the reverse): everything cd_t and cd_p are made of; the divisions by the
+ * lengths, the / 2, weights and the batch reduction are the caller's, on (B,4).  idx_xy (B,n1) / idx_yx (B,n2) int32
+ * receive the index where each minimum is attained -- what pdr_chamfer_loss_grad needs; both may be NULL for a
+ * loss-only call (exactly one NULL: PDR_EINVAL).  TWO launches on `stream` (the search with per-workgroup partial sums
+ * into the workspace, then a finishing launch), no atomics, no allocation, no synchronisation: capturable.
+ *   - minima and indices are those of pdr_chamfer_nn / pdr_chamfer_nn_ragged, bit for bit: the knn expression
+ *     fma(dz, dz, fma(dy, dy, dx * dx)) on the differences, strict <, first minimum wins.  A padded query and a query
+ *     whose opposite cloud is empty get index -1 (and add nothing).
+ *   - lengths1 / lengths2 follow pdr_knn_points_ragged: int64 arrays of B entries in DEVICE memory, read by the kernels
+ *     only and clamped there to [0, n1] / [0, n2]; NULL = every cloud is full; n1 / n2 stay the row strides.  Rows at or
+ *     beyond a length are never queries, never candidates and never read for their value (NaN included).  A pair with
+ *     an empty side has all four sums +0.0f.
+ *   - the sums are deterministic (no floating-point atomics): the order is fixed by the code and is a function of the
+ *     two lengths only -- per thread in ascending query order, a fixed tree per 1024-query block, then the blocks in
+ *     ascending order.  A ragged pair gets the bits of the dense call on the two slices; NULL or full lengths give the
+ *     bits of the call without lengths; asking for the indices changes no bit of sums.  The longest chain of dependent
+ *     fp32 roundings is 12 + ceil(max(n1, n2) / 1024) -- 28 for n <= 16384 -- and every addend is non-negative:
+ *     sums[0:2] is within 28 * 2^-24 relative of the exact sum of the fp32 minima, sums[2:4] (one more rounding per
+ *     addend, the sqrt) within 30 * 2^-24 of the exact sum of their square roots.
+ *   - workspace: pdr_chamfer_loss_workspace_bytes(B, n1, n2) bytes of device memory, 4-byte aligned; positive for
+ *     supported positive sizes, non-decreasing in each argument, 0 for B <= 0 and for sizes the call refuses.  Its
+ *     contents are private and undefined afterwards; two calls in flight at once need a workspace each.
+ *   - validation, decided on the host before any launch, in this order: a negative size: PDR_EINVAL; B == 0: PDR_OK,
+ *     nothing launched, no pointer looked at; n1 <= 0 or n2 <= 0: PDR_EINVAL; sizes the kernels do not index --
+ *     B > 65535, max(n1, n2) > 2^24 or B max(n1, n2) >= 2^31 --: PDR_EUNSUPPORTED; NULL x / y / sums, exactly one NULL
+ *     index array, a NULL workspace or one that is not 4-byte aligned: PDR_EINVAL. */
+size_t pdr_chamfer_loss_workspace_bytes(int B, int n1, int n2);
+int pdr_chamfer_loss(const float *x, const float *y, const int64_t *lengths1, const int64_t *lengths2,
+                     int B, int n1, int n2, float *sums, int *idx_xy, int *idx_yx, void *workspace,
+                     pdr_stream_t stream);
+/* Backward of pdr_chamfer_loss w.r.t. both clouds.  grad_sums (B,4) f32 = (g0, g1, g2, g3) = d(loss)/d(sums[b]); idx_xy /
+ * idx_yx are the arrays the forward wrote; grad_x (B,n1,3) and grad_y (B,n2,3) are fully written.  The coefficient on
+ * a squared distance is
+ *     w_xy[i] = g0 + (g2 == 0 ? 0 : g2 * 0.5 / sqrt(d_xy[i])),     w_yx[j] = g1 + (g3 == 0 ? 0 : g3 * 0.5 / sqrt(d_yx[j]))
+ * with d recomputed from x, y and the saved index by the knn expression (the bits the forward saw; no distance tensor
+ * is saved), and
+ *     grad_x[b,i] = fl(2 w_xy[i]) (x_i - y_idx_xy[i])  -  sum over j with idx_yx[j] == i, j ascending, of
+ *                   fl(2 w_yx[j]) (y_j - x_i)
+ * grad_y being the mirror image.  Every product is rounded before its add (no fused multiply-add); an element starts
+ * from its query term (+0.0f when that index is -1) and the scattered terms are added after it in ascending source
+ * order, so the same input gives the same bits.  ONE launch, no workspace, no atomics of any kind, no allocation, no
+ * synchronisation: capturable.  Each output element is written exactly once.
+ *   - zero coefficient: when g2 (g3) is exactly 0 the sqrt term is not evaluated; a cd_t-only loss never sees 0 * inf.
+ *   - zero distance: when d == 0 the sqrt term contributes exactly 0.  A subgradient choice -- the direction x - y is 0
+ *     there -- that DEPARTS from the torch composition sqrt(d).backward(), which gives inf * 0 = NaN for a coincident
+ *     pair; mirrored condition clouds and x == y make coincident pairs real.
+ *   - padded rows of either cloud and all rows of a pair with an empty side get +0.0f; a padded source is never added.
+ *     An index outside [0, n) of the opposite cloud is skipped and reaches no memory.
+ *   - how: an inverse scan.  One thread owns a destination point, the opposite direction's index array streams through
+ *     LDS and the thread compares every entry with its own index: n1 n2 integer compares per cloud and direction.
+ *   - validation: the forward's size checks and codes, then a NULL x / y / idx_xy / idx_yx / grad_sums / grad_x /
+ *     grad_y: PDR_EINVAL. */
+int pdr_chamfer_loss_grad(const float *x, const float *y, const int64_t *lengths1, const int64_t *lengths2,
+                          const int *idx_xy, const int *idx_yx, const float *grad_sums, int B, int n1, int n2,
+                          float *grad_x, float *grad_y, pdr_stream_t stream);
 /* Voxel-grid occupancy counters of a SET of clouds (the loop of entropy_of_occupancy_grid,
  * pointnet2/models/pvd/metrics/evaluation_metrics.py:198-237, which queries a KD-tree per cloud and counts in Python):
  *     clouds (S,n,3) f32  ->  counters[c] += points of all clouds whose nearest kept grid cell is c,

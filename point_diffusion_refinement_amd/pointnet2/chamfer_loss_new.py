@@ -13,6 +13,8 @@ All distances are SQUARED; cd_p takes the square root per point before the mean;
 the F-score threshold is applied to squared distances.
 fscore / calc_cd / Chamfer_F1 take the lengths too: precision, recall and the means are over each cloud's valid
 points, and a cloud of length 0 yields 0 for every metric.
+calc_cd_fused / ChamferLoss (not in the reference) are calc_cd's cd_p / cd_t as a training loss on kernels of their own
+(pdr_chamfer_loss, pdr_chamfer_loss_grad): three launches for forward plus backward, bit-reproducible.
 """
 from typing import Union
 
@@ -211,6 +213,56 @@ def calc_cd(output, gt, calc_f1=False, f1_threshold=0.0001, output_lengths=None,
         f1, _, _ = fscore(d1, d2, threshold=f1_threshold)
         return cd_p, cd_t, f1
     return cd_p, cd_t
+
+
+def calc_cd_fused(output, gt, output_lengths=None, gt_lengths=None):
+    """(cd_p, cd_t), each (B,), with calc_cd's definitions and argument order (d1 = gt->output) as a TRAINING LOSS:
+    differentiable w.r.t. both clouds, three launches for forward plus backward (pdr_chamfer_loss,
+    pdr_chamfer_loss_grad) and bit-reproducible without any switch.  The means are over the valid points; a sample with
+    an empty cloud gives 0.  Where calc_cd's cd_p has a NaN gradient -- a coincident pair -- this one's sqrt term is 0.
+    train.py:518 becomes calc_cd_fused(X, refined_X)[loss_idx].mean()."""
+    if not (torch.is_tensor(output) and torch.is_tensor(gt)) or output.ndim != 3 or gt.ndim != 3:
+        raise ValueError("Expected points to be of shape (N, P, 3)")
+    if output.shape[0] != gt.shape[0]:
+        raise ValueError("output and gt must hold the same number of clouds")
+    on = lambda l, ref: None if l is None else l.to(device=ref.device, dtype=torch.int64).contiguous()
+    output_lengths, gt_lengths = on(output_lengths, output), on(gt_lengths, gt)
+    sums = _ext.chamfer_loss_sums(gt.contiguous(), output.contiguous(), gt_lengths, output_lengths)
+    count = lambda l, ref: float(ref.shape[1]) if l is None else l.clamp(0, ref.shape[1]).clamp(min=1).to(sums.dtype)
+    n_gt, n_out = count(gt_lengths, gt), count(output_lengths, output)
+    cd_p = (sums[:, 2] / n_gt + sums[:, 3] / n_out) / 2
+    cd_t = sums[:, 0] / n_gt + sums[:, 1] / n_out
+    return cd_p, cd_t
+
+
+class ChamferLoss(nn.Module):
+    """calc_cd_fused as a module: `loss_type` 'cd_t' | 'cd_p' picks the metric, `weights` (B,) scales each cloud's
+    value, `reduction` 'mean' | 'sum' | None reduces over the batch ('mean' divides by the sum of the weights when
+    they are given, as chamfer_distance does)."""
+
+    def __init__(self, loss_type="cd_t", reduction="mean"):
+        super().__init__()
+        if loss_type not in ("cd_t", "cd_p"):
+            raise ValueError('loss_type must be one of ["cd_t", "cd_p"]')
+        if reduction is not None and reduction not in ("mean", "sum"):
+            raise ValueError('reduction must be one of ["mean", "sum"] or None')
+        self.loss_type, self.reduction = loss_type, reduction
+
+    def forward(self, output, gt, output_lengths=None, gt_lengths=None, weights=None):
+        if weights is not None:
+            if weights.ndim != 1 or weights.size(0) != output.shape[0]:
+                raise ValueError("weights must be of shape (N,).")
+            if not (weights >= 0).all():
+                raise ValueError("weights cannot be negative.")
+        cd_p, cd_t = calc_cd_fused(output, gt, output_lengths, gt_lengths)
+        loss = cd_t if self.loss_type == "cd_t" else cd_p
+        if weights is not None:
+            loss = loss * weights.to(loss)
+        if self.reduction is None:
+            return loss
+        if self.reduction == "sum":
+            return loss.sum()
+        return loss.sum() / (weights.to(loss).sum() if weights is not None else loss.shape[0])
 
 
 class Chamfer_F1(nn.Module):

@@ -344,6 +344,68 @@ def chamfer_nn(x, y, x_lengths=None, y_lengths=None):
     return dx, ix, dy, iy
 
 
+def _chamfer_loss_forward(x, y, x_lengths, y_lengths, with_idx):
+    B, n1, _ = x.shape
+    n2 = y.shape[1]
+    lib = _lib.load()
+    sums = torch.empty((B, 4), dtype=torch.float32, device=x.device)
+    ix = torch.empty((B, n1), dtype=torch.int32, device=x.device) if with_idx else None
+    iy = torch.empty((B, n2), dtype=torch.int32, device=x.device) if with_idx else None
+    nbytes = lib.pdr_chamfer_loss_workspace_bytes(B, n1, n2)     # block partials of this call, a torch allocation
+    ws = torch.empty((max(int(nbytes), 4),), dtype=torch.uint8, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.check(lib.pdr_chamfer_loss(x.data_ptr(), y.data_ptr(), _ptr(x_lengths), _ptr(y_lengths), B, n1, n2,
+                                        sums.data_ptr(), _ptr(ix), _ptr(iy), ws.data_ptr(), _stream()), "chamfer_loss")
+    return sums, ix, iy
+
+
+class _ChamferLossSums(torch.autograd.Function):
+    """pdr_chamfer_loss with its int32 indices saved for pdr_chamfer_loss_grad (one launch, order-fixed: the same bits
+    whatever set_deterministic says)."""
+
+    @staticmethod
+    def forward(ctx, x, y, x_lengths, y_lengths):
+        sums, ix, iy = _chamfer_loss_forward(x, y, x_lengths, y_lengths, True)
+        ctx.save_for_backward(x, y, x_lengths, y_lengths, ix, iy)
+        return sums
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_sums):
+        x, y, x_lengths, y_lengths, ix, iy = ctx.saved_tensors
+        B, n1, _ = x.shape
+        gs = grad_sums.contiguous().float()
+        gx, gy = torch.empty_like(x), torch.empty_like(y)
+        with torch.cuda.device(x.device):
+            _lib.check(_lib.load().pdr_chamfer_loss_grad(x.data_ptr(), y.data_ptr(), _ptr(x_lengths), _ptr(y_lengths),
+                                                         ix.data_ptr(), iy.data_ptr(), gs.data_ptr(), B, n1,
+                                                         y.shape[1], gx.data_ptr(), gy.data_ptr(), _stream()),
+                       "chamfer_loss_grad")
+        return gx, gy, None, None
+
+
+def chamfer_loss_sums(x, y, x_lengths=None, y_lengths=None):
+    """The four sums a Chamfer loss is made of, differentiable w.r.t. both clouds (pdr_chamfer_loss /
+    pdr_chamfer_loss_grad): (B,n1,3), (B,n2,3) -> sums (B,4) f32 =
+    (sum_i d_xy, sum_j d_yx, sum_i sqrt d_xy, sum_j sqrt d_yx) with d_xy[i] = min_j |x_i - y_j|^2, over the valid
+    points.  `x_lengths` / `y_lengths` ((B,) int64 on the clouds' device, None = full) as in chamfer_nn; a pair with an
+    empty side gives four zeros.  Under torch.no_grad(), or when neither cloud requires a gradient, no index is
+    computed.  Where the torch composition's gradient of sqrt is NaN -- a coincident pair, d = 0 -- this one's sqrt
+    term is 0."""
+    _req(x, "x", torch.float32)
+    _req(y, "y", torch.float32)
+    _same_device(x, y)
+    _req_xyz(x, "x")
+    _req_xyz(y, "y")
+    if x.shape[0] != y.shape[0]:
+        raise RuntimeError("chamfer_loss_sums: (B,n,3) clouds with equal batch size")
+    _req_lengths(x_lengths, "x_lengths", x)
+    _req_lengths(y_lengths, "y_lengths", y)
+    if torch.is_grad_enabled() and (x.requires_grad or y.requires_grad):
+        return _ChamferLossSums.apply(x, y, x_lengths, y_lengths)
+    return _chamfer_loss_forward(x, y, x_lengths, y_lengths, False)[0]
+
+
 def chamfer_pairwise(x, y, x_lengths=None, y_lengths=None, symmetric=False):
     """All-pairs Chamfer distance between two sets of clouds in one launch (pdr_chamfer_pairwise):
     (S,n,3), (R,m,3) -> cd (S,R) f32, cd[s,r] = mean_i min_j |x_s,i - y_r,j|^2 + mean_j min_i (the same); not
