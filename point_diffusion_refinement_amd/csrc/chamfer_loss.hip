@@ -8,7 +8,7 @@
 // over the valid points -- everything cd_t and cd_p are made of -- and, when a gradient will be asked for, the two
 // int32 nearest-neighbour index arrays.  The backward takes d(loss)/d(sums) and writes grad_x and grad_y in ONE launch.
 //
-// FORWARD.  The search is nn1_kernel's (neighbors.hip): a thread owns 2 QP queries as packed fp32 pairs, the candidate
+// FORWARD.  The search is the packed scan of nn1_scan.h, nn1_kernel's loop (neighbors.hip): a thread owns 2 QP queries as packed fp32 pairs, the candidate
 // cloud streams through LDS in 1024-point float4 tiles every lane reads at the same address, the distance is PDR_ACC3
 // on the differences, per 8-point chunk only a running minimum is kept and the ONE recorded chunk of a query is
 // rescanned in ascending order with a strict `<`: every minimum and index has the bits pdr_chamfer_nn returns (a valid
@@ -45,7 +45,7 @@
 // the ascending order and the reproducible bits fall out of the loop.  Padded rows and rows of a pair with an empty
 // side get +0.0f; an index outside [0, n) matches no destination and reaches no memory.
 //
-// GRID.  Forward: (ceil(max(n1, n2) / (512 QP)), B, 2 directions) workgroups of 256 threads; the compiler reports 74
+// GRID.  Forward: (ceil(max(n1, n2) / (512 QP)), B, 2 directions) workgroups of 256 threads; the compiler reports 72
 // VGPRs with index recovery and 58 without, no scratch, 16,416 B of LDS.  Splitting a (cloud, direction) over
 // workgroups is what the workspace and the finishing launch pay for: measured forward + backward through calc_cd_fused
 // at (B, n1, n2) = (32, 2048, 2048) / (8, 16384, 16384), 0.306 / 1.504 ms against 0.383 / 14.6 ms with one workgroup
@@ -54,12 +54,12 @@
 //
 // SIZES.  Refused with PDR_EUNSUPPORTED: B > 65535 (grid y), B max(n1, n2) >= 2^31 (int32 positions) and
 // max(n1, n2) > 2^24 (keeps every query / candidate position and the block count of the finishing loop in int).
-#include "pdr_common.h"
+#include "nn1_scan.h"
 
 namespace {
 
-constexpr int kTile = 1024;    // candidate points per LDS tile (forward), index entries per LDS tile (backward)
-constexpr int kChunk = 8;      // candidates per unrolled step; tiles are padded to a multiple with +inf points
+using pdr::cloud_len;
+using pdr::kTile;              // candidate points per LDS tile (forward) and index entries per LDS tile (backward)
 constexpr int kMaxN = 1 << 24;
 
 #ifndef PDR_CDL_QP
@@ -70,15 +70,6 @@ constexpr int kMaxN = 1 << 24;
 #endif
 
 constexpr int kBlockQ = 256 * 2 * PDR_CDL_QP;   // queries per block = per partial sum
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-// the length rule of pdr_knn_points_ragged (neighbors.hip cloud_len): device int64, clamped to [0, n], NULL = full
-__device__ __forceinline__ int loss_cloud_len(const int64_t* __restrict__ len, int b, int n) {
-  if (!len) return n;
-  const int64_t v = len[b];
-  return v < 0 ? 0 : (v > n ? n : static_cast<int>(v));
-}
 
 // partial sums: (B, 2 directions, nblk blocks, {sum d, sum sqrt d})
 __device__ __forceinline__ size_t partial_at(int b, int dir, int nblk, int blk) {
@@ -100,113 +91,33 @@ __global__ __launch_bounds__(256) void chamfer_loss_kernel(const float* __restri
   const float* queries = (dir ? y : x) + static_cast<size_t>(b) * nq * 3;
   const float* c = (dir ? x : y) + static_cast<size_t>(b) * nc * 3;
   int* idx = dir ? idx_yx : idx_xy;
-  const int nqe = loss_cloud_len(dir ? len_y : len_x, b, nq);
-  const int nce_all = loss_cloud_len(dir ? len_x : len_y, b, nc);
+  const int nqe = cloud_len(dir ? len_y : len_x, b, nq);
+  const int nce_all = cloud_len(dir ? len_x : len_y, b, nc);
   // the grid covers max(n1, n2); a block beyond this direction's padded size has nothing to write (uniform)
   for (int blk = blockIdx.x; blk * QPB < nq; blk += gridDim.x) {
     const int q0 = blk * QPB + threadIdx.x;        // thread t owns queries q0 + 256 i (coalesced loads / stores)
     const int nce = blk * QPB < nqe ? nce_all : 0; // a block of padded queries scans nothing
-    f32x2 qx[QP], qy[QP], qz[QP], best[QP];
-    int bchunk[NQ];
+    // slots beyond the length shadow the last valid query (row 0 of an empty cloud; its value is never used)
+    pdr::Nn1State<QP> st;
+    pdr::nn1_load(st, queries, q0, nqe - 1);
+    pdr::nn1_scan<QP, WITH_IDX>(st, c, nce, tile);
+    float acc[2] = {0.0f, 0.0f};                                 // sum d, sum sqrt d
 #pragma unroll
-    for (int p = 0; p < QP; ++p) {
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        // slots beyond the length shadow the last valid query (row 0 of an empty cloud; its value is never used)
-        const int j = max(min(q0 + 256 * (2 * p + h), nqe - 1), 0);
-        const float* q = queries + static_cast<size_t>(j) * 3;
-        qx[p][h] = q[0];
-        qy[p][h] = q[1];
-        qz[p][h] = q[2];
-        bchunk[2 * p + h] = 0;
-      }
-      best[p] = f32x2{__builtin_inff(), __builtin_inff()};
+    for (int s = 0; s < NQ; ++s) {
+      const int j = q0 + 256 * s;
+      // a valid query with a finite minimum; anything else adds +0.0f (exact).  Ascending query order.
+      const bool valid = j < nqe && st.best[s >> 1][s & 1] < __builtin_inff();
+      const float d = valid ? st.best[s >> 1][s & 1] : 0.0f;
+      acc[0] += d;
+      acc[1] += __builtin_sqrtf(d);
+      if (WITH_IDX && j < nq)                                    // -1: padded query / empty opposite cloud
+        idx[static_cast<size_t>(b) * nq + j] = valid ? pdr::nn1_recover(st, s, c, nce).i : -1;
     }
-    for (int k0 = 0; k0 < nce; k0 += kTile) {
-      const int kn = (nce - k0) < kTile ? (nce - k0) : kTile;
-      const int kpad = (kn + kChunk - 1) / kChunk * kChunk;     // <= kTile: kTile is a multiple of kChunk
-      __syncthreads();
-      for (int t = threadIdx.x; t < kpad; t += 256) {
-        const float* s = c + static_cast<size_t>(k0 + min(t, kn - 1)) * 3;
-        // slots beyond the cloud: +inf coordinates -> distance +inf, never below any minimum
-        tile[t] = t < kn ? make_float4(s[0], s[1], s[2], 0.0f)
-                         : make_float4(__builtin_inff(), __builtin_inff(), __builtin_inff(), 0.0f);
-      }
-      __syncthreads();
-      for (int t0 = 0; t0 < kpad; t0 += kChunk) {
-        f32x2 cm[QP];
-#pragma unroll
-        for (int p = 0; p < QP; ++p) cm[p] = f32x2{__builtin_inff(), __builtin_inff()};
-#pragma unroll
-        for (int u = 0; u < kChunk; ++u) {
-          const float4 pt = tile[t0 + u];
-#pragma unroll
-          for (int p = 0; p < QP; ++p) {
-            const f32x2 dx = qx[p] - pt.x, dy = qy[p] - pt.y, dz = qz[p] - pt.z;
-            f32x2 d = dx * dx;                                   // PDR_ACC3 on both halves of the pair
-            d = __builtin_elementwise_fma(dy, dy, d);
-            d = __builtin_elementwise_fma(dz, dz, d);
-            cm[p] = __builtin_elementwise_min(cm[p], d);
-          }
-        }
-#pragma unroll
-        for (int p = 0; p < QP; ++p) {
-#pragma unroll
-          for (int h = 0; h < 2; ++h) {
-            const bool up = cm[p][h] < best[p][h];               // strict: the EARLIEST chunk holding the minimum
-            best[p][h] = up ? cm[p][h] : best[p][h];
-            if (WITH_IDX) bchunk[2 * p + h] = up ? k0 + t0 : bchunk[2 * p + h];
-          }
-        }
-      }
-    }
-    float acc = 0.0f, acc_sqrt = 0.0f;
-#pragma unroll
-    for (int p = 0; p < QP; ++p) {
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        const int j = q0 + 256 * (2 * p + h);
-        // a valid query with a finite minimum; anything else adds +0.0f (exact).  Ascending query order.
-        const bool valid = j < nqe && best[p][h] < __builtin_inff();
-        const float d = valid ? best[p][h] : 0.0f;
-        acc += d;
-        acc_sqrt += __builtin_sqrtf(d);
-        if (WITH_IDX && j < nq) {
-          // index recovery: rescan the recorded chunk (kChunk points from global memory, ascending, strict <)
-          int li = -1;
-          if (valid) {
-            const float x0 = qx[p][h], y0 = qy[p][h], z0 = qz[p][h];
-            float lb = __builtin_inff();
-            const int cs = bchunk[2 * p + h];
-            for (int u = 0; u < kChunk; ++u) {
-              const int k = cs + u;
-              if (k < nce) {
-                const float* s = c + static_cast<size_t>(k) * 3;
-                const float dx = x0 - s[0], dy = y0 - s[1], dz = z0 - s[2];
-                const float dd = PDR_ACC3(dx, dy, dz);
-                if (dd < lb) {
-                  lb = dd;
-                  li = k;
-                }
-              }
-            }
-          }
-          idx[static_cast<size_t>(b) * nq + j] = li;             // -1: padded query / empty opposite cloud
-        }
-      }
-    }
-    acc = pdr::wave_sum_f32(acc);
-    acc_sqrt = pdr::wave_sum_f32(acc_sqrt);
-    __syncthreads();                                             // wsum of the previous block has been read
-    if ((threadIdx.x & 63) == 0) {
-      wsum[threadIdx.x >> 6] = acc;
-      wsum[4 + (threadIdx.x >> 6)] = acc_sqrt;
-    }
-    __syncthreads();
+    pdr::block_sum_256(acc, wsum);
     if (threadIdx.x == 0) {
       float* out = partial + partial_at(b, dir, nblk, blk);
-      out[0] = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
-      out[1] = (wsum[4] + wsum[5]) + (wsum[6] + wsum[7]);
+      out[0] = acc[0];
+      out[1] = acc[1];
     }
   }
 }
@@ -219,7 +130,7 @@ __global__ __launch_bounds__(256) void chamfer_loss_finish(const float* __restri
   const int o = blockIdx.x * 256 + threadIdx.x;
   if (o >= B * 4) return;
   const int b = o >> 2, dir = o & 1, comp = (o >> 1) & 1;
-  const int lx = loss_cloud_len(len_x, b, n1), ly = loss_cloud_len(len_y, b, n2);
+  const int lx = cloud_len(len_x, b, n1), ly = cloud_len(len_y, b, n2);
   const int nqe = dir ? ly : lx;
   const int nb = (lx > 0 && ly > 0) ? (nqe + block_q - 1) / block_q : 0;   // a pair with an empty side: +0.0f
   const float* p = partial + partial_at(b, dir, nblk, 0) + comp;
@@ -255,7 +166,7 @@ __global__ __launch_bounds__(256) void chamfer_loss_grad_kernel(const float* __r
   const int* idx_own = (side ? idx_yx : idx_xy) + static_cast<size_t>(b) * nd;   // destination -> its nearest source
   const int* idx_src = (side ? idx_xy : idx_yx) + static_cast<size_t>(b) * ns;   // source -> its nearest destination
   float* grad = (side ? grad_y : grad_x) + static_cast<size_t>(b) * nd * 3;
-  const int lx = loss_cloud_len(len_x, b, n1), ly = loss_cloud_len(len_y, b, n2);
+  const int lx = cloud_len(len_x, b, n1), ly = cloud_len(len_y, b, n2);
   const int nde = (lx > 0 && ly > 0) ? (side ? ly : lx) : 0;     // a pair with an empty side: every row +0.0f
   const int nse = side ? lx : ly;
   const int i = blockIdx.x * 256 + threadIdx.x;

@@ -7,7 +7,8 @@
 //
 //   cd[s,r] = (1/n_s) sum_i min_j |x_s,i - y_r,j|^2  +  (1/m_r) sum_j min_i |x_s,i - y_r,j|^2
 //
-// Both terms are ONE routine, direction_sum(queries, candidates): the queries of a direction live in registers as
+// Both terms are ONE routine, direction_sum(queries, candidates), on the packed scan of nn1_scan.h without its chunk
+// recording (no index is asked for): the queries of a direction live in registers as
 // packed fp32 PAIRS (two queries per v_pk_add / v_pk_mul / v_pk_fma, each half IEEE-exact), the candidate cloud streams
 // through LDS in 1024-point float4 tiles every lane reads at the same address (one broadcast read per point), and per
 // (query, candidate) only the distance and a share of a minimum are issued (gfx950 has no packed fp32 minimum: the
@@ -34,25 +35,15 @@
 // need a workspace or atomics.  symmetric: the workgroups of s > r exit at once, the owner of s <= r writes cd[s,r] and
 // cd[r,s].  A thread holds 8 queries per pass (PDR_CDP_QP = 4 pairs): one broadcast LDS read serves 8 distances;
 // measured at 256 x 256 clouds of 2048 points 55.3 ms against 59.0 ms with 4 queries (profiles/pairwise_cd.txt).
-#include "pdr_common.h"
+#include "nn1_scan.h"
 
 namespace {
 
-constexpr int kTile = 1024;    // candidate points per LDS tile
-constexpr int kChunk = 8;      // candidates per unrolled step; tiles are padded to a multiple with +inf points
+using pdr::kTile;
 
 #ifndef PDR_CDP_QP
 #define PDR_CDP_QP 4           // query PAIRS per thread and pass (lab builds: -DPDR_CDP_QP=2)
 #endif
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-// the length rule of pdr_knn_points_ragged (neighbors.hip cloud_len): device int64, clamped to [0, n], NULL = full
-__device__ __forceinline__ int pair_cloud_len(const int64_t* __restrict__ len, int b, int n) {
-  if (!len) return n;
-  const int64_t v = len[b];
-  return v < 0 ? 0 : (v > n ? n : static_cast<int>(v));
-}
 
 // sum over the queries q[0 .. nq) of min over the candidates c[0 .. nc) of the squared distance; nq, nc >= 1.
 // Returned in every thread.  Rows at or beyond nq / nc are never loaded.
@@ -60,61 +51,19 @@ template <int QP>
 __device__ __forceinline__ float direction_sum(const float* __restrict__ q, int nq, const float* __restrict__ c,
                                                int nc, float4* __restrict__ tile, float* __restrict__ wsum) {
   constexpr int NQ = 2 * QP;
-  float acc = 0.0f;
-  for (int q0 = 0; q0 < nq; q0 += 256 * NQ) {
-    // thread t owns queries q0 + t + 256 i (coalesced loads); slots beyond nq shadow the last query and are not summed
-    f32x2 qx[QP], qy[QP], qz[QP], best[QP];
+  float acc[1] = {0.0f};
+  for (int pass = 0; pass < nq; pass += 256 * NQ) {
+    // thread t owns queries q0 + 256 i (coalesced loads); slots beyond nq shadow the last query and are not summed
+    const int q0 = pass + threadIdx.x;
+    pdr::Nn1State<QP> st;
+    pdr::nn1_load(st, q, q0, nq - 1);
+    pdr::nn1_scan<QP, false>(st, c, nc, tile);
 #pragma unroll
-    for (int p = 0; p < QP; ++p) {
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        const int j = min(q0 + static_cast<int>(threadIdx.x) + 256 * (2 * p + h), nq - 1);
-        qx[p][h] = q[j * 3 + 0];
-        qy[p][h] = q[j * 3 + 1];
-        qz[p][h] = q[j * 3 + 2];
-      }
-      best[p] = f32x2{__builtin_inff(), __builtin_inff()};
-    }
-    for (int k0 = 0; k0 < nc; k0 += kTile) {
-      const int kn = (nc - k0) < kTile ? (nc - k0) : kTile;
-      const int kpad = (kn + kChunk - 1) / kChunk * kChunk;     // <= kTile: kTile is a multiple of kChunk
-      __syncthreads();
-      for (int t = threadIdx.x; t < kpad; t += 256) {
-        const float* s = c + (k0 + min(t, kn - 1)) * 3;
-        // slots beyond the cloud: +inf coordinates -> distance +inf, never below any minimum
-        tile[t] = t < kn ? make_float4(s[0], s[1], s[2], 0.0f)
-                         : make_float4(__builtin_inff(), __builtin_inff(), __builtin_inff(), 0.0f);
-      }
-      __syncthreads();
-      for (int t0 = 0; t0 < kpad; t0 += kChunk) {
-#pragma unroll
-        for (int u = 0; u < kChunk; ++u) {
-          const float4 pt = tile[t0 + u];
-#pragma unroll
-          for (int p = 0; p < QP; ++p) {
-            const f32x2 dx = qx[p] - pt.x, dy = qy[p] - pt.y, dz = qz[p] - pt.z;
-            f32x2 d = dx * dx;                                   // PDR_ACC3 on both halves of the pair
-            d = __builtin_elementwise_fma(dy, dy, d);
-            d = __builtin_elementwise_fma(dz, dz, d);
-            best[p] = __builtin_elementwise_min(best[p], d);
-          }
-        }
-      }
-    }
-#pragma unroll
-    for (int p = 0; p < QP; ++p) {
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        const bool valid = q0 + static_cast<int>(threadIdx.x) + 256 * (2 * p + h) < nq;
-        acc += valid ? best[p][h] : 0.0f;                        // ascending query order; + 0.0f is exact
-      }
-    }
+    for (int s = 0; s < NQ; ++s)
+      acc[0] += q0 + 256 * s < nq ? st.best[s >> 1][s & 1] : 0.0f;   // ascending query order; + 0.0f is exact
   }
-  acc = pdr::wave_sum_f32(acc);
-  __syncthreads();                                               // wsum of the previous direction has been read
-  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  return (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
+  pdr::block_sum_256(acc, wsum);
+  return acc[0];
 }
 
 template <int QP>
@@ -128,7 +77,7 @@ __global__ __launch_bounds__(256) void chamfer_pairs_kernel(const float* __restr
   if (pair >= static_cast<long long>(S) * R) return;            // uniform: the last grid row may be partial
   const int s = static_cast<int>(pair / R), r = static_cast<int>(pair % R);
   if (symmetric && s > r) return;                                // written by the owner of (r, s)
-  const int ns = pair_cloud_len(len_x, s, n), mr = pair_cloud_len(len_y, r, m);
+  const int ns = pdr::cloud_len(len_x, s, n), mr = pdr::cloud_len(len_y, r, m);
   float v = 0.0f;                                                // a pair with an empty side: calc_cd's 0
   if (ns > 0 && mr > 0) {
     const float* xs = x + static_cast<size_t>(s) * n * 3;

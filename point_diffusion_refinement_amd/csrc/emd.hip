@@ -77,8 +77,8 @@ __device__ __forceinline__ PairLen pair_len(const int64_t* __restrict__ len1,
                                             const int64_t* __restrict__ len2, int b, int n, int m) {
   PairLen p{n, m};
   if (RAGGED) {
-    if (len1) { const int64_t v = len1[b]; p.n = v < 0 ? 0 : (v > n ? n : static_cast<int>(v)); }
-    if (len2) { const int64_t v = len2[b]; p.m = v < 0 ? 0 : (v > m ? m : static_cast<int>(v)); }
+    p.n = pdr::cloud_len(len1, b, n);
+    p.m = pdr::cloud_len(len2, b, m);
     if (p.n == 0 || p.m == 0) p.n = p.m = 0;
   }
   return p;

@@ -14,23 +14,19 @@
 // both the reference three_nn cascade and the knn contract in include/pdr_hip.h.
 #include <cstdlib>
 
-#include "pdr_common.h"
+#include "nn1_scan.h"
 
 namespace {
 
-constexpr int kTile = 1024;
+using pdr::cloud_len;
+using pdr::f32x2;
+using pdr::kTile;
 
 enum DistModel { kSum3 = 0, kAcc3 = 1 };
 
-// Per-cloud lengths (pytorch3d lengths1 / lengths2; pdr_knn_points_ragged, pdr_chamfer_nn_ragged): the RAGGED
-// instantiations of the three search kernels read cloud b's length here, on the device, clamped to [0, n]; n stays
-// the row stride.  Queries at or beyond their cloud's length search nothing and get the padding output, rows at or
-// beyond the searched cloud's length are never candidates.  NULL = every cloud is full.
-__device__ __forceinline__ int cloud_len(const int64_t* __restrict__ len, int b, int n) {
-  if (!len) return n;
-  const int64_t v = len[b];
-  return v < 0 ? 0 : (v > n ? n : static_cast<int>(v));
-}
+// Per-cloud lengths (pdr_knn_points_ragged, pdr_chamfer_nn_ragged): the RAGGED instantiations of the three search
+// kernels read cloud b's length with pdr::cloud_len.  Queries at or beyond their cloud's length search nothing and get
+// the padding output, rows at or beyond the searched cloud's length are never candidates.
 
 template <int K, int MODEL, typename IdxT, bool KNN_PAD, bool RAGGED = false>
 __global__ __launch_bounds__(256) void nn_search_kernel(const float* __restrict__ queries,
@@ -139,7 +135,7 @@ __global__ __launch_bounds__(256) void nn_search_kernel(const float* __restrict_
 //      + one 64-bit compare per candidate; ranks < K are the answer in ascending order, equal distances by lower
 //      index, exactly the contract of the sorted-insertion kernel (bit-identical outputs, tested).
 // More than 64 candidates (massive exact ties) take an exact K-round minimum extraction instead.
-// RAGGED (cloud_len above): slots at or beyond the cloud's length hold +inf like the slots beyond nc, are never
+// RAGGED (pdr::cloud_len): slots at or beyond the cloud's length hold +inf like the slots beyond nc, are never
 // candidates and never win the extraction.  A cloud shorter than 57 points leaves an 8-lane group without a point and
 // T = +inf: all its (< 64) points are candidates and the rank path orders them.  A cloud shorter than K has fewer
 // candidates than K and takes the extraction, whose exhausted key reads as index -1: such slots are written as
@@ -391,22 +387,15 @@ int launch_knn_wave(const KnnPlan& p, const float* x, const float* y, int B, int
 }
 
 // ---- K = 1 (Chamfer) ------------------------------------------------------------------------
-// chamfer_loss_new.py:149-167 asks knn_points(K=1) twice (x -> y and y -> x); 8.39 M pair evaluations per
-// 2048^2 cloud pair, so the kernel is bound by VALU ISSUE SLOTS per pair, not by memory.  The generic kernel above
-// spends ~9 slots per pair (6 distance + compare + 2 selects) plus one LDS read.  Here:
-//   * a thread owns 2 QP queries held as QP float PAIRS: the distance expression runs on packed fp32
-//     (v_pk_add / v_pk_mul / v_pk_fma: two queries per instruction, each lane IEEE-exact, same ACC3 expression
-//     tree as the generic kernel -> bit-identical distances);
-//   * every LDS point (one ds_read, broadcast) serves all 2 QP queries;
-//   * no per-pair index bookkeeping: per chunk of CH points only the running minimum (v_min / v_min3) is kept,
-//     and once per chunk `chunk_min < best` (STRICT) records the chunk; when the scan is over the ONE recorded
-//     chunk of each query is rescanned in ascending order with strict `<`, which returns the first (lowest-index)
-//     point attaining the minimum = "first minimum wins" (chamfer3D.cu:26-129, pdr_hip.h knn contract).
-// ~4 issue slots per pair.  blockIdx.z selects the direction so both searches of a Chamfer evaluation are one launch.
-// RAGGED (cloud_len above): len_a / len_b bound xa / xb per cloud, as queries in one direction and as candidates in
+// The packed scan described in nn1_scan.h: a workgroup owns 512 QP consecutive queries of one (cloud, direction).
+// blockIdx.z selects the direction so both searches of a Chamfer evaluation are one launch.
+// This kernel spells the scan out instead of calling pdr::nn1_load / nn1_scan / nn1_recover, and the two spellings
+// must stay equal (tests/test_chamfer_loss_gpu.py holds the indices of the loss kernel, which calls them, to this
+// kernel's): on the header the compiler emits the same inner loop, staging and rescan, yet a launch
+// of 128 workgroups (32 pairs of 2048^2) measured 122.0 us against 119.6 us, outside the 0.9 us spread of this form
+// (profiles/nn1_scan_ab.txt).
+// RAGGED (pdr::cloud_len): len_a / len_b bound xa / xb per cloud, as queries in one direction and as candidates in
 // the other; padded queries and queries of an empty cloud get (0, pad_idx): -1 for knn_points, 0 for Chamfer.
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
 template <int QP, typename IdxT, bool RAGGED = false>
 __global__ __launch_bounds__(256) void nn1_kernel(const float* __restrict__ xa, const float* __restrict__ xb,
                                                   int na, int nb, float* __restrict__ da,
@@ -414,7 +403,7 @@ __global__ __launch_bounds__(256) void nn1_kernel(const float* __restrict__ xa, 
                                                   IdxT* __restrict__ ib,
                                                   const int64_t* __restrict__ len_a = nullptr,
                                                   const int64_t* __restrict__ len_b = nullptr, int pad_idx = -1) {
-  constexpr int CH = 8;
+  constexpr int CH = pdr::kChunk;
   constexpr int NQ = 2 * QP;                       // queries per thread
   __shared__ float4 tile[kTile];
   const int dir = blockIdx.z;

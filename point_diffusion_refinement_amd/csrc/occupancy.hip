@@ -52,12 +52,6 @@ constexpr int kWaves = kThreads / 64;
 constexpr int kHeadBytes = 32 * 8 + kThreads * 4 + kThreads * 4 + 16 + 1024 * 4;   // axd, queue, qcell, ctrl, kept
 constexpr int kNone = 0x7fffffff;
 
-__device__ __forceinline__ int occ_cloud_len(const int64_t* __restrict__ len, int b, int n) {
-  if (!len) return n;
-  const int64_t v = len[b];
-  return v < 0 ? 0 : (v > n ? n : static_cast<int>(v));
-}
-
 // step 1 for one axis; p is finite.  All lanes read the same LDS address (broadcast).
 __device__ __forceinline__ int nearest_axis(const double* __restrict__ axd, int R, double p) {
   int best = 0;
@@ -137,7 +131,7 @@ __global__ __launch_bounds__(kThreads) void occupancy_kernel(const float* __rest
   int* counts = reinterpret_cast<int*>(kept + 1024);
 
   const int s = blockIdx.x;
-  const int len = occ_cloud_len(lengths, s, n);
+  const int len = pdr::cloud_len(lengths, s, n);
   if (len == 0) return;                                          // uniform: an empty cloud touches nothing
   const float* cloud = clouds + static_cast<size_t>(s) * n * 3;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;

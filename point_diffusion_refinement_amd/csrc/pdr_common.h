@@ -139,6 +139,15 @@ __device__ __forceinline__ float wave_sum_f32(float v) {
 
 __device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
 
+// Per-cloud lengths (pytorch3d lengths1 / lengths2; every pdr_*_ragged call and the calls that take `lengths`): cloud
+// b's length is read here, on the device, as int64 and clamped to [0, n]; n stays the row stride.  NULL = every cloud
+// is full.
+__device__ __forceinline__ int cloud_len(const int64_t* __restrict__ len, int b, int n) {
+  if (!len) return n;
+  const int64_t v = len[b];
+  return v < 0 ? 0 : (v > n ? n : static_cast<int>(v));
+}
+
 __device__ __forceinline__ unsigned bitrev(unsigned v, int bits) {
   return bits == 0 ? 0u : (__brev(v) >> (32 - bits));
 }
