@@ -66,7 +66,8 @@ typedef void *pdr_stream_t; /* hipStream_t */
  *                pdr_gather_add* / pdr_gather_moments*) is new; pdr_occupancy_grid is new; pdr_fused_layer_pool_plan (the same
  *                for the two pooled entry points) is new; pdr_scatter_workspace_bytes and the four deterministic backward
  *                twins pdr_*_grad_det are new; pdr_chamfer_loss_workspace_bytes / pdr_chamfer_loss / pdr_chamfer_loss_grad
- *                are new. */
+ *                are new; pdr_fps_ragged_workspace_bytes / pdr_fps_ragged_plan / pdr_furthest_point_sampling_ragged are
+ *                new. */
 int pdr_version(void);
 /* last hip error string seen by this thread after a PDR_ELAUNCH ("" if none) */
 const char *pdr_last_error(void);
@@ -112,6 +113,41 @@ int pdr_furthest_point_sampling(const float *xyz, int B, int N, int m,
  * reported.  out = {family (0 resident, 1 wave, 2 lean, 3 stream), threads per cloud T, points per thread PPT (0: the
  * stream kernel strides), slots = R Q with R = pdr_opt_n_threads(N), Q = ceil(N / R)}.  N <= 0: PDR_EINVAL. */
 int pdr_fps_plan(int N, int out[4]);
+
+/* Furthest point sampling of a PADDED batch with per-cloud lengths, optionally of every cloud together with its mirror
+ * image, in ONE launch that also writes the picked rows (the length-aware, mirroring form of the call above;
+ * pytorch3d's sample_farthest_points(lengths=...) with the reference kernel's tie order).
+ *   xyz (B,N,3) f32, lengths (B) i64 or NULL  ->  idx (B,m) i32, rows (B,m,4) f32 (may be NULL; 16-byte aligned)
+ *   - lengths follows pdr_knn_points_ragged: an int64 array of B entries in DEVICE memory, read only by the kernel and
+ *     clamped there to [0, N]; NULL = every cloud is full; N stays the row stride.  The host never reads it, so the call
+ *     neither synchronises nor allocates, is one launch and is capturable: a replayed graph follows the lengths then in
+ *     memory.
+ *   - mirror_axis is -1 (no mirror) or 0 / 1 / 2.  Cloud b is a VIRTUAL cloud of V_b = L_b points, or 2 L_b with a
+ *     mirror: virtual point k < L_b is xyz[b,k], virtual point k >= L_b is xyz[b,k-L_b] with the sign bit of coordinate
+ *     mirror_axis flipped (what `partial * sign` gives, -0.0 included).  Nothing of size 2N is materialised.
+ *   - idx holds the picks as virtual indices; row j of `rows` is the picked virtual point's (x, y, z, tag), tag = +1 for
+ *     an original and -1 for a mirrored point (+1 without a mirror).
+ *   - row b of idx is, index for index, what pdr_furthest_point_sampling returns for the materialised virtual cloud
+ *     (1, V_b, 3) and the same m: the tie order (which does not depend on the length: for every N the reference's rank
+ *     is the order of the key (bitrev9(k % 512), k / 512)), the |p|^2 <= 1e-3 exclusion, "all excluded -> 0", m > V_b
+ *     (rounds after exhaustion are ties at the current maximum) and idx[b,0] = 0.
+ *   - rows at or beyond a length are never read for their value (NaN included); a cloud of length 0 gets idx = -1 and
+ *     rows = 0 in every slot; every output element is written exactly once; the same input gives the same bits, and no
+ *     option of pdr_set_option changes which kernel runs.
+ *   - two forms, chosen on the host from V = N * (mirror ? 2 : 1) and reported by pdr_fps_ragged_plan (host only; the
+ *     launch reads the same decision): out = {family (0 resident, 1 stream), threads per cloud, points per thread (0:
+ *     the stream kernel strides), dynamic LDS bytes}.  Resident (V <= 12288): no workspace, the cloud in LDS, running
+ *     distances in registers, one workgroup per cloud; the reported points per thread are the launch's maximum -- every
+ *     workgroup runs the loop built for ceil(V_b / threads) rounded up to 2, 4, 8, 12 or 16, so a short cloud does not
+ *     pay for N.  Stream (above): running distances in `temp`, pdr_fps_ragged_workspace_bytes = B * V floats.
+ *   - validation, on the host before any launch, in this order: B < 0, N <= 0, m < 0 or mirror_axis outside [-1, 2]:
+ *     PDR_EINVAL; B == 0 or m == 0: PDR_OK, nothing launched, no pointer looked at; V > 2^20 or B * max(V, m) >= 2^31:
+ *     PDR_EUNSUPPORTED; NULL xyz / idx, a NULL temp where the workspace size is positive, or a misaligned rows:
+ *     PDR_EINVAL.  The workspace query returns 0 for B <= 0 and for sizes the call refuses. */
+size_t pdr_fps_ragged_workspace_bytes(int B, int N, int mirror_axis);
+int pdr_fps_ragged_plan(int N, int mirror_axis, int out[4]);
+int pdr_furthest_point_sampling_ragged(const float *xyz, const int64_t *lengths, int B, int N, int mirror_axis, int m,
+                                       float *temp, int *idx, float *rows, pdr_stream_t stream);
 
 /* ---- gather -----------------------------------------------------------------
  * gather_points(points (B,C,N), idx (B,m)) -> out (B,C,m)   sampling.cpp:15-38

@@ -27,6 +27,9 @@ SIGNATURES = {
     "pdr_fps_workspace_bytes": (_Z, [_I, _I]),
     "pdr_furthest_point_sampling": (_I, [_P, _I, _I, _I, _P, _P, _P]),
     "pdr_fps_plan": (_I, [_I, _P]),
+    "pdr_fps_ragged_workspace_bytes": (_Z, [_I, _I, _I]),
+    "pdr_fps_ragged_plan": (_I, [_I, _I, _P]),
+    "pdr_furthest_point_sampling_ragged": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
     "pdr_gather_points": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),
     "pdr_gather_points_grad": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),
     "pdr_ball_query": (_I, [_P, _P, _I, _I, _I, _F, _I, _P, _P, _P]),

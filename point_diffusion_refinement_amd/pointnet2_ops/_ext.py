@@ -86,6 +86,35 @@ def furthest_point_sampling(points, nsamples):
     return out
 
 
+def furthest_point_sampling_ragged(points, nsamples, lengths=None, mirror_axis=None, return_rows=False):
+    """Length-aware FPS of a padded batch, optionally of every cloud together with its mirror image, in one launch:
+    (B,N,3) f32 [, lengths (B,) i64 on the device] -> idx (B,nsamples) i32 [, rows (B,nsamples,4) f32].
+
+    Cloud b is the virtual cloud of its first lengths[b] rows, followed -- when `mirror_axis` is 0 / 1 / 2 -- by the
+    same rows with that coordinate negated; `idx` indexes the virtual cloud and row j of `rows` is the picked point's
+    (x, y, z, tag), tag -1 for a mirrored point.  Each row of `idx` is what `furthest_point_sampling` returns for the
+    materialised virtual cloud; padding rows are never read, a cloud of length 0 gets idx -1 / rows 0
+    (pdr_furthest_point_sampling_ragged of include/pdr_hip.h)."""
+    if mirror_axis is not None and mirror_axis not in (0, 1, 2):
+        raise ValueError("mirror_axis must be None, 0, 1 or 2, got %r" % (mirror_axis,))
+    _req(points, "points", torch.float32)
+    _req_xyz(points, "points")
+    _req_lengths(lengths, "lengths", points)
+    axis = -1 if mirror_axis is None else int(mirror_axis)
+    B, N, _ = points.shape
+    m = int(nsamples)
+    lib = _lib.load()
+    idx = torch.empty((B, m), dtype=torch.int32, device=points.device)
+    rows = torch.empty((B, m, 4), dtype=torch.float32, device=points.device) if return_rows else None
+    ws = lib.pdr_fps_ragged_workspace_bytes(B, N, axis)
+    temp = torch.empty((ws // 4,), dtype=torch.float32, device=points.device) if ws else None
+    with torch.cuda.device(points.device):
+        _lib.check(lib.pdr_furthest_point_sampling_ragged(points.data_ptr(), _ptr(lengths), B, N, axis, m, _ptr(temp),
+                                                          idx.data_ptr(), _ptr(rows), _stream()),
+                   "furthest_point_sampling_ragged")
+    return (idx, rows) if return_rows else idx
+
+
 def gather_points(points, idx):
     """(B,C,N) f32, (B,m) i32 -> (B,C,m)   [sampling.cpp:15-38]"""
     _req(points, "points", torch.float32)

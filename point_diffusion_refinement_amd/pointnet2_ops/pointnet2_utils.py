@@ -50,6 +50,23 @@ class FurthestPointSampling(Function):
 furthest_point_sample = FurthestPointSampling.apply
 
 
+class FurthestPointSamplingRagged(Function):
+    @staticmethod
+    def forward(ctx, xyz, npoint, lengths):
+        out = _ext.furthest_point_sampling_ragged(xyz, npoint, lengths=lengths)
+        ctx.mark_non_differentiable(out)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        return ()
+
+
+# (B,N,3) padded clouds, npoint, lengths (B,) int64 or None -> (B,npoint) i32: FPS of each cloud's first lengths[b]
+# rows (pytorch3d's sample_farthest_points(lengths=...) with this library's tie order); a cloud of length 0 gets -1
+furthest_point_sample_ragged = FurthestPointSamplingRagged.apply
+
+
 class GatherOperation(Function):
     @staticmethod
     def forward(ctx, features, idx):
