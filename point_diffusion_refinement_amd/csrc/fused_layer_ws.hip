@@ -8,13 +8,17 @@
 // issue-stalled 59 % of their cycles.  Here the two jobs belong to different waves of a 512-thread
 // workgroup:
 //   waves 0-3  CONSUMERS  own the accumulators; per chunk: barrier, ds_read + v_mfma only.
-//   waves 4-7  PRODUCERS  global -> registers -> prologue -> LDS for chunk g+1 while chunk g is being
-//                         multiplied; the loads of chunk g+2 are issued before the barrier and fly
-//                         through the next chunk period; they never touch an accumulator.
+//   waves 4-7  PRODUCERS  activation rows: global -> registers -> prologue -> LDS for chunk g+1 while
+//                         chunk g is being multiplied; the loads of chunk g+2 are issued before the
+//                         barrier and fly through the next chunk period.  Weight chunks need no math and
+//                         go global -> LDS by DMA (global_load_lds): issued right after the barrier
+//                         that frees their stage, retired by a counted vmcnt before the next one, which
+//                         is a raw s_barrier so that the row prefetch stays in flight across it.  They
+//                         never touch an accumulator.
 // LDS holds two stages; ONE barrier per chunk hands stage g to the consumers and stage g+1 back to
 // the producers.  Workgroups are persistent over row tiles and the chunk sequence runs across tile
 // boundaries, so the first chunk of the next tile is staged during the epilogue of the current one.
-// Register budget 128 (consumers: 64 accumulators, producers: one chunk in flight) = 4 waves / SIMD.
+// Register budget 128 (consumers: 64 accumulators, producers: one chunk of rows in flight) = 4 waves / SIMD.
 // Epilogue: accumulators start at the bias, half tiles are transposed through LDS into dwordx4 row
 // stores, the GroupNorm moments of the tile are folded across waves with an LDS ticket (no barrier
 // that the producers would have to join).  The reasons behind each of these choices (VALU
@@ -45,6 +49,14 @@ __device__ unsigned long long pdr_lab_wg[2048][3];
   } while (0)
 #else
 #define PDR_T(role, slot) do {} while (0)
+#endif
+
+// Weight chunks reach LDS by DMA (global_load_lds).  -DPDR_LAB_W_REGS (tools/lab A/B sessions): through registers
+// (global_load_dwordx4 + ds_write_b128 per quad, 16 producer registers), the earlier form.
+#ifdef PDR_LAB_W_REGS
+constexpr bool kWDma = false;
+#else
+constexpr bool kWDma = true;
 #endif
 
 // identity prologue parameters for layers without scale / shift / add: read like the real per-channel
@@ -340,9 +352,49 @@ __global__ __launch_bounds__(512, (ws_waves_per_simd<RT, CT, RADD, SPLIT>())) vo
     constexpr bool RG = RADD && GATH != 0;
     float4 Rrv[APT4], Rrv2[1];
     f32x4 Rrrv[RADD ? APT4 : 1], Rrrv2[1], Rqr1, Rqr2;   // Rqr: kNN-form residual, rows of the d2 / weight channels   // (vector values: conditional float4 struct copies go through scratch)
-    f32x4 Rrw[WPT4];
+    f32x4 Rrw[kWDma ? 1 : WPT4];                         // (lab build PDR_LAB_W_REGS only: W through registers)
     float Rps[4], Rph[4], Rpa[4];
     int Rkmax = KC, Rcvalid = 4;   // valid k rows of the chunk; valid channels of this thread's float4
+    // W of the chunk at cursor c (kmax valid k rows): uniform base + this thread's byte offsets.  Every clamp is on
+    // the SOURCE: rows beyond a partial last chunk re-read its last row, columns beyond ldw the row's last float4.
+    auto w_source = [&](const Cur& c, int kmax, unsigned (&wo)[WPT4]) __attribute__((always_inline)) -> const char* {
+      if (SPLIT || kmax == KC) {                                     // uniform
+#pragma unroll
+        for (int i = 0; i < WPT4; ++i) wo[i] = SPLIT ? static_cast<unsigned>(pt + PT * i) * 16u : w_off[i];
+      } else {
+        const int nmax = ldw - n0 - 4;   // last in-row float4 offset
+#pragma unroll
+        for (int i = 0; i < WPT4; ++i) {
+          const int e = pt + PT * i;
+          const int k = e / TN4, n4 = e - k * TN4;
+          wo[i] = static_cast<unsigned>(min(k, kmax - 1) * ldw + min(4 * n4, nmax)) * 4u;
+        }
+      }
+      // SPLIT: chunk image number (column block, chunk) of the packed weights; 16 KiB each, copied linearly
+      return SPLIT ? reinterpret_cast<const char*>(Wt) + (static_cast<long>(blockIdx.y) * ldw + c.ci) * (2L * TN * 64)
+                   : reinterpret_cast<const char*>(Wt + static_cast<long>(c.cbase + c.ks) * ldw + n0);
+    };
+    // dma_w: the W chunk at cursor c -> stage st by LDS-DMA (global_load_lds, 16 bytes per lane; no register, no
+    // ds_write).  Element e = pt + 256 i of the chunk is byte 16 e of the stage's W image in both layouts (fp32
+    // Bs[st][k][4 n4] with e = k TN4 + n4; the packed f16x3 image is linear), so instruction i of a wave writes the
+    // 1 KiB at 16 (64 (wave - 4) + 256 i): a wave-uniform base + lane x 16, the only destination form the DMA has.
+    // A wave whose 64 elements lie beyond the image issues nothing (the cut falls on a wave boundary).
+    static_assert((KC * TN4) % 64 == 0, "W image: whole 64-lane DMA pieces");
+    auto dma_w = [&](const Cur& c, int st) __attribute__((always_inline)) {
+      unsigned wo[WPT4];
+      const char* wb = w_source(c, min(KC, in.seg[c.sg].C - c.ks), wo);
+      typedef __attribute__((address_space(3))) unsigned char lds_byte;
+      lds_byte* img;
+      if constexpr (SPLIT) img = (lds_byte*)&sm.B[st][0][0];
+      else img = (lds_byte*)&sm.Bs[st][0][0];
+#pragma unroll
+      for (int i = 0; i < WPT4; ++i) {
+        const int e0 = 64 * (wave - 4) + PT * i;                     // first element of this wave's piece (uniform)
+        if (KC * TN4 % PT == 0 || e0 < KC * TN4)
+          __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(wb + wo[i]), img + 16 * e0, 16,
+                                           0, 0);
+      }
+    };
     // fetch: chunk at cursor c -> registers (address arithmetic + loads only)
     auto fetch = [&](const Cur& c) __attribute__((always_inline)) {
       const int lt = row_tile(c.tile);
@@ -408,11 +460,7 @@ __global__ __launch_bounds__(512, (ws_waves_per_simd<RT, CT, RADD, SPLIT>())) vo
           seg.ptr + (f_g ? static_cast<long>(b) * seg.g_nsrc : (row0 >> shift)) * seg.ld + c.ks);
       const int zrow = f_g ? seg.g_zrow - b * seg.g_nsrc : 0;    // the zero row, relative to this cloud
       const int v0d = (f_g && seg.gV0) ? static_cast<int>(seg.gV0 - seg.gV) : 0;
-      // SPLIT: chunk image number (column block, chunk) of the packed weights; 16 KiB each, copied linearly
-      const char* wb = SPLIT ? reinterpret_cast<const char*>(Wt) +
-                                   (static_cast<long>(blockIdx.y) * ldw + c.ci) * (2L * TN * 64)
-                             : reinterpret_cast<const char*>(Wt + static_cast<long>(c.cbase + c.ks) * ldw + n0);
-      unsigned ao[APT4], ro[RADD ? APT4 : 1], wo[WPT4], po[4], vo = 0;
+      unsigned ao[APT4], ro[RADD ? APT4 : 1], po[4], vo = 0;
       if (Rkmax == KC && nvalid == TM) {
         // ---- fast path (uniform): the precomputed per-thread offsets
         if (off_sg != c.sg) {
@@ -440,8 +488,6 @@ __global__ __launch_bounds__(512, (ws_waves_per_simd<RT, CT, RADD, SPLIT>())) vo
 #pragma unroll
           for (int i = 0; i < APT4; ++i) ro[i] = r_off[i];
         }
-#pragma unroll
-        for (int i = 0; i < WPT4; ++i) wo[i] = SPLIT ? static_cast<unsigned>(pt + PT * i) * 16u : w_off[i];
       } else {
         // ---- general path: partial chunk (last of a segment) or partial row tile
         const int cl = 4 * vc4;                                   // relative to ks
@@ -462,14 +508,6 @@ __global__ __launch_bounds__(512, (ws_waves_per_simd<RT, CT, RADD, SPLIT>())) vo
           }
           ao[i] = static_cast<unsigned>(row * seg.ld + clc) * 4u;
           if constexpr (RADD) ro[i] = static_cast<unsigned>(r * in.rseg.ld + clc) * 4u;
-        }
-        const int nmax = ldw - n0 - 4;   // last in-row float4 offset
-#pragma unroll
-        for (int i = 0; i < WPT4; ++i) {
-          const int e = pt + PT * i;
-          const int k = e / TN4, n4 = e - k * TN4;
-          wo[i] = SPLIT ? static_cast<unsigned>(pt + PT * i) * 16u
-                        : static_cast<unsigned>(min(k, Rkmax - 1) * ldw + min(4 * n4, nmax)) * 4u;
         }
       }
       if (Rkmax == KC) {
@@ -540,8 +578,12 @@ __global__ __launch_bounds__(512, (ws_waves_per_simd<RT, CT, RADD, SPLIT>())) vo
 #pragma unroll
         for (int i = 0; i < APT4; ++i) Rrrv[i] = *reinterpret_cast<const f32x4*>(rb + ro[i]);
       }
+      if constexpr (!kWDma) {
+        unsigned wo[WPT4];
+        const char* wb = w_source(c, Rkmax, wo);
 #pragma unroll
-      for (int i = 0; i < WPT4; ++i) Rrw[i] = *reinterpret_cast<const f32x4*>(wb + wo[i]);
+        for (int i = 0; i < WPT4; ++i) Rrw[i] = *reinterpret_cast<const f32x4*>(wb + wo[i]);
+      }
     };
     // commit: prologue math + LDS stores into stage st.  The staging instructions compete with the
     // consumers' MFMAs for issue slots (measured ~20 cycles per instruction next to two MFMA-bound
@@ -622,7 +664,9 @@ __global__ __launch_bounds__(512, (ws_waves_per_simd<RT, CT, RADD, SPLIT>())) vo
       else if (has_pre) stage_a(F(), T(), T());
       else if (has_add) stage_a(F(), F(), T());
       else stage_a(F(), F(), F());
-      if constexpr (SPLIT) {
+      if constexpr (kWDma) {
+        // (W: dma_w)
+      } else if constexpr (SPLIT) {
         // the packed image is already in LDS layout ([hi | lo][col][64 B], granules swizzled): linear copy
         unsigned char* wdst = &sm.B[st][0][0];
 #pragma unroll
@@ -641,9 +685,30 @@ __global__ __launch_bounds__(512, (ws_waves_per_simd<RT, CT, RADD, SPLIT>())) vo
     // the next chunk, barrier.  The staging math is spread over all four producer waves because its
     // LATENCY (not its issue cost) is what can delay the barrier: next to two MFMA-bound waves a
     // VALU instruction waits ~a whole MFMA issue slot.
+    //
+    // W takes no part in that: it needs no math, so it goes global -> LDS by DMA.  A DMA writes its stage when it
+    // lands, so the one of chunk g+1 is ISSUED after B(g) (stage g+1 free) and must have landed before B(g+1).  The
+    // VM counter retires in order and the DMA is older than the A prefetch of chunk g+2 that follows it, so the
+    // iteration ends with a COUNTED wait -- vmcnt(number of vector-memory instructions of that fetch) -- which
+    // retires the DMA and leaves the prefetch in flight, then a raw s_barrier.  (__syncthreads() in a wave with a
+    // DMA pending waits vmcnt(0): the prefetch would be drained every chunk.)  The count is the fetch's fewest
+    // instructions: 3 prologue-parameter quads + APT4 rows (+ APT4 residual rows, + the gathered residual's query row
+    // and kNN rows), and the query row (+ 2 kNN rows) of a gathered segment.  Chunks that issue more (a partial last
+    // chunk: 12 parameter dwords; a tile's first chunk: its indices; any spill) only wait for a few of their own
+    // oldest loads as well -- a count too small is safe, one too large is not.  The consumers read stage g+1 after
+    // B(g+1), one barrier after the wait that retired its DMA.  (tools/lab/ws_resources.py checks, per instantiation,
+    // that the compiled waits carry these counts and that no register load sits between the barrier and the DMA.)
+    // What the compiler adds: while a global_load_lds is outstanding it waits vmcnt(0) at the first use of ANY load
+    // result, so commit()'s first row use also waits for the DMA issued just before it (an L2 round trip; the row
+    // prefetch is issued after commit() and is not affected).  DESIGN.md 4.1.
+    constexpr int NVM = 3 + APT4 + (RADD ? APT4 : 0) + (RG ? 1 + (GATH == 2 ? 2 : 0) : 0);
+    constexpr int NVM_G = NVM + 1 + (KNN ? 2 : 0);
     Cur co{tile_first, 0, 0, 0, 0};
+    // (chunk 0: stage 0 is free from the start.  Rows first, DMA second -- the order the loop's back edge arrives in,
+    // so the compiler's wait for the rows in commit() is a counted one on both ways in; B(0)'s wait retires the DMA)
     fetch(co);
-    for (int g = 0; g < G; ++g) {
+    if constexpr (kWDma) dma_w(co, 0);
+    for (int g = 0;; ++g) {
       PDR_T(1, 4 * g + 0);
 #ifdef PDR_LAB_TRACE
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -654,7 +719,17 @@ __global__ __launch_bounds__(512, (ws_waves_per_simd<RT, CT, RADD, SPLIT>())) vo
       advance(co, g + 1 < G);
       fetch(co);                                    // past the end: re-reads the last chunk
       PDR_T(1, 4 * g + 2);
-      __syncthreads();                                 // B(g): stage g full, stage g+1 free
+      if constexpr (kWDma) {
+        // (lgkmcnt(0): this wave's A stores; the raw barrier carries no fence of its own)
+        if (GATH != 0 && Rgath) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(NVM_G) : "memory");   // uniform
+        else asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(NVM) : "memory");
+        __builtin_amdgcn_s_barrier();               // B(g): stage g full, stage g+1 free
+        if (g + 1 >= G) break;                      // (no DMA may be pending when the workgroup gives its LDS back)
+        dma_w(co, (g + 1) & 1);
+      } else {
+        __syncthreads();                               // B(g): stage g full, stage g+1 free
+        if (g + 1 >= G) break;
+      }
     }
     return;
   }
