@@ -940,8 +940,9 @@ int pdr_embed_linear(const float *x, int ldx, const float *ts, int ts_stride, co
  * scratch: >= out[1] floats of pdr_point_chain_plan; sync: >= 2 B + 1 ints, ZEROED ONCE by the caller -- the launch leaves
  * them zero (sync[2 B] != 0 afterwards: a workgroup gave up waiting; never seen, kept so that a fault cannot hang the
  * device).  Supported: n in {16, 32, 64, 128, 256}, every width a multiple of 16 G with column blocks of whole groups,
- * 16-byte aligned pointers, leading dimensions multiples of 4; otherwise PDR_EUNSUPPORTED (the caller runs the layers one
- * by one).  Exact fp32 MFMA (v_mfma_f32_16x16x4_f32); equals the layer-by-layer evaluation up to fp32 summation order. */
+ * 16-byte aligned pointers (segments, Wt, bias, add, out, and scratch when n_layers > 1), leading dimensions (seg.ld,
+ * ldw, add_ld, ldo) multiples of 4; otherwise PDR_EUNSUPPORTED (the caller runs the layers one by one).  A leading
+ * dimension below its width, widths that do not chain and NULL out / scratch / sync are PDR_EINVAL.  Exact fp32 MFMA (v_mfma_f32_16x16x4_f32); equals the layer-by-layer evaluation up to fp32 summation order. */
 typedef struct {
   const float *ptr;     /* (B n, ld) */
   int C, ld;

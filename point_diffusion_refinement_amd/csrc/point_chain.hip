@@ -477,11 +477,15 @@ int plan_chain(const pdr_point_chain_t& p, int B, int n, ChainPlan* out) {
     if (L.gamma) {
       if (!L.beta || L.groups <= 0 || L.Cn <= 0 || L.Cn > L.main_cols || L.Cn % L.groups != 0) return PDR_EINVAL;
     }
-    if (L.add && (L.add_ld < L.main_cols || L.add_ld % 4 != 0 || !aligned16(L.add))) return PDR_EINVAL;
+    if (L.add && L.add_ld < L.main_cols) return PDR_EINVAL;
+    if (L.add && (L.add_ld % 4 != 0 || !aligned16(L.add))) return PDR_EUNSUPPORTED;
   }
   const pdr_chain_layer_t& last = p.layer[p.n_layers - 1];
   if (p.residual && p.layer[0].Cout - p.layer[0].main_cols != last.main_cols) return PDR_EINVAL;
-  if (p.ldo < last.main_cols || p.ldo % 4 != 0 || !aligned16(p.out)) return PDR_EINVAL;
+  if (p.ldo < last.main_cols) return PDR_EINVAL;
+  if (p.ldo % 4 != 0 || !aligned16(p.out)) return PDR_EUNSUPPORTED;
+  // (the next layer reads the published blocks as 16-byte quads)
+  if (p.n_layers > 1 && !aligned16(p.scratch)) return PDR_EUNSUPPORTED;
   if (!(n == 16 || n == 32 || n == 64 || n == 128 || n == 256)) return PDR_EUNSUPPORTED;
   const int NRT = n / 16, WR = NRT < 4 ? NRT : 4, WC = 4 / WR;
   for (int G = 8; G >= 1; G >>= 1) {

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests.chain_cases import chain_case as _chain_case, launch_chain as _launch_chain
 from tests.golden.det_weights import fill_deterministic
 from tests.golden.tiny_config import small_fused_config
 
@@ -1751,76 +1752,8 @@ def test_embed_select_and_step_table(cuda):
 
 
 # ---- round 6: a chain of per-point layers as ONE launch (pdr_point_chain) ------------------------------
-def _chain_case(seed, B, n, seg_widths, widths, residual, relu_pre, device, with_add=True):
-    """Random chain problem + its float64 evaluation layer by layer (conv -> [ReLU] -> GroupNorm(32 groups) -> [ReLU] ->
-    + add row, residual = extra columns of layer 0 added at the end)."""
-    g = torch.Generator().manual_seed(seed)
-    segs = [torch.randn(B * n, (c + 3) // 4 * 4, generator=g) for c in seg_widths]
-    x = torch.cat([s[:, :c] for s, c in zip(segs, seg_widths)], 1).double()
-    layers, cin, h, res = [], sum(seg_widths), x, None
-    for i, c in enumerate(widths):
-        cout = c + (widths[-1] if (i == 0 and residual) else 0)
-        W = torch.randn(cin, cout, generator=g) / cin ** 0.5
-        bias = torch.randn(cout, generator=g) * 0.1
-        gamma, beta = torch.rand(c, generator=g) + 0.5, torch.randn(c, generator=g) * 0.1
-        add = torch.randn(B, c + 8, generator=g) if with_add else None
-        cn = c - c % 32                                         # MyGroupNorm: a tail of c % 32 channels passes through
-        y = h @ W.double() + bias.double()
-        if i == 0 and residual:
-            res, y = y[:, c:], y[:, :c]
-        f = y.relu() if relu_pre else y
-        z = f.clone()
-        fn = f[:, :cn].view(B, n, cn).transpose(1, 2)                                      # (B, cn, n)
-        z[:, :cn] = torch.nn.functional.group_norm(fn, 32, gamma[:cn].double(), beta[:cn].double(), 1e-5) \
-            .transpose(1, 2).reshape(B * n, cn)
-        if not relu_pre:
-            z = z.relu()
-        if add is not None:
-            z = z + add[:, :c].double().repeat_interleave(n, 0)
-        layers.append(dict(W=W, bias=bias, gamma=gamma, beta=beta, add=add, cn=cn, cout=cout, c=c))
-        h, cin = z, c
-    if residual:
-        h = h + res
-    return segs, layers, h
-
-
-def _launch_chain(segs, seg_widths, layers, B, n, residual, relu_pre, device):
-    lib = _lib.load()
-    keep = [s.to(device) for s in segs]
-    ch = _lib.PointChain()
-    ch.n_layers, ch.n_seg, ch.residual = len(layers), len(segs), int(residual)
-    for i, (t, c) in enumerate(zip(keep, seg_widths)):
-        ch.seg[i].ptr, ch.seg[i].C, ch.seg[i].ld = t.data_ptr(), c, t.shape[1]
-    for i, Ld in enumerate(layers):
-        L = ch.layer[i]
-        dv = {k: (v.to(device).contiguous() if torch.is_tensor(v) else v) for k, v in Ld.items()}
-        keep.append(dv)
-        L.Wt, L.bias, L.ldw, L.Cin, L.Cout, L.main_cols = dv["W"].data_ptr(), dv["bias"].data_ptr(), dv["cout"], \
-            dv["W"].shape[0], dv["cout"], dv["c"]
-        L.gamma, L.beta, L.groups, L.Cn, L.eps = dv["gamma"].data_ptr(), dv["beta"].data_ptr(), 32, dv["cn"], 1e-5
-        L.relu_pre, L.relu_post = int(relu_pre), int(not relu_pre)
-        if dv["add"] is not None:
-            L.add, L.add_ld = dv["add"].data_ptr(), dv["add"].shape[1]
-    plan = (ctypes.c_long * 4)()
-    rc = lib.pdr_point_chain_plan(ctypes.byref(ch), B, n, plan)
-    if rc != _lib.PDR_OK:
-        return rc, None, None
-    out = torch.full((B * n, layers[-1]["c"] + 4), float("nan"), device=device)
-    scratch = torch.empty(max(int(plan[1]), 4), device=device)
-    sync = torch.zeros(int(plan[2]), dtype=torch.int32, device=device)
-    ch.out, ch.ldo, ch.scratch, ch.sync = out.data_ptr(), out.shape[1], scratch.data_ptr(), sync.data_ptr()
-    outs = []
-    for _ in range(3):                                   # the counters are left zero: launch after launch, same bytes
-        out.fill_(float("nan"))
-        _lib.check(lib.pdr_point_chain(ctypes.byref(ch), B, n, torch.cuda.current_stream().cuda_stream), "point_chain")
-        torch.cuda.synchronize()
-        assert sync.tolist() == [0] * sync.numel(), "cluster counters not restored / a workgroup timed out"
-        outs.append(out[:, :layers[-1]["c"]].clone())
-    assert torch.equal(outs[0], outs[1]) and torch.equal(outs[0], outs[2])
-    assert bool(torch.isnan(out[:, layers[-1]["c"]:]).all())              # nothing written behind the output columns
-    return rc, outs[0], list(plan)
-
-
+# (the case builder, the float64 reference and the launch helper live in tests/chain_cases.py, which also walks the
+# kernel's whole dispatch table: tests/test_chain_dispatch_plan.py, tests/test_chain_dispatch_gpu.py)
 @pytest.mark.parametrize("B,n,seg_widths,widths,residual,relu_pre", [
     (32, 64, (256, 256, 3), (256, 256), True, False),      # the 64-point level's second MLP (fp4: 515 -> 256 -> 256)
     (32, 256, (128, 256, 3), (256, 256), True, False),     # the 256-point level's (fp3: 387 -> 256 -> 256)
@@ -1919,16 +1852,18 @@ def test_point_chain_under_uneven_load_and_warm_caches(cuda):
         assert e < 2e-5, (it, e)          # (a stale block would be off by O(1); small inputs round at 5e-6)
 
 
-def test_fp_block_second_mlp_as_one_launch_equals_the_layer_launches(cuda, monkeypatch):
+@pytest.mark.parametrize("B", [2, 33])
+def test_fp_block_second_mlp_as_one_launch_equals_the_layer_launches(cuda, monkeypatch, B):
     """The feature-propagation blocks of the 64- / 256-point levels evaluate their second MLP (conv -> GroupNorm -> ReLU ->
     + t embedding -> conv -> GroupNorm -> ReLU -> + condition embedding -> + residual conv) as ONE pdr_point_chain launch
     (fused_network.POINT_CHAINS); eps of the full DDPM network with and without it agree to fp32 summation order, and the
-    chain really ran (two launches per cached forward at B = 2: n = 64 and n = 256)."""
+    chain really ran (two launches per cached forward: n = 64 and n = 256).  B = 2: clusters of 8 workgroups; B = 33:
+    B G <= 256 leaves clusters of 4 with column blocks of 64 + 64 (four column tiles per wave), no multiple of 8 clouds."""
     torch.manual_seed(0)
     net = PointNet2CloudCondition(ddpm_pointnet_config()).eval().to(cuda)
     fused = FN.FusedCloudConditionNet(net)
-    x, cond, label = synthetic_batch(2, seed=5, device=cuda)
-    ts = torch.tensor([300.0, 20.0], device=cuda)
+    x, cond, label = synthetic_batch(B, seed=5, device=cuda)
+    ts = torch.tensor([300.0, 20.0], device=cuda).repeat((B + 1) // 2)[:B].contiguous()
     lib = _lib.load()
     calls = []
     real = lib.pdr_point_chain
