@@ -67,7 +67,7 @@ typedef void *pdr_stream_t; /* hipStream_t */
  *                for the two pooled entry points) is new; pdr_scatter_workspace_bytes and the four deterministic backward
  *                twins pdr_*_grad_det are new; pdr_chamfer_loss_workspace_bytes / pdr_chamfer_loss / pdr_chamfer_loss_grad
  *                are new; pdr_fps_ragged_workspace_bytes / pdr_fps_ragged_plan / pdr_furthest_point_sampling_ragged are
- *                new. */
+ *                new; pdr_attention_pool_cf_plan / pdr_attention_pool_cf / pdr_attention_pool_cf_grad are new. */
 int pdr_version(void);
 /* last hip error string seen by this thread after a PDR_ELAUNCH ("" if none) */
 const char *pdr_last_error(void);
@@ -321,6 +321,54 @@ int pdr_chamfer_loss(const float *x, const float *y, const int64_t *lengths1, co
 int pdr_chamfer_loss_grad(const float *x, const float *y, const int64_t *lengths1, const int64_t *lengths2,
                           const int *idx_xy, const int *idx_yx, const float *grad_sums, int B, int n1, int n2,
                           float *grad_x, float *grad_y, pdr_stream_t stream);
+/* The pooling tail of AttentionModule.forward (pointnet2_ops/attention.py:71-77) for the TRAINABLE path, channel-first
+ * and differentiable (pdr_attention_pool below is the channel-last, forward-only form of the fused sampler):
+ *     scores, values (B,C,N,K) f32, dense, K innermost (what weight_conv / feat_out_conv write);
+ *     counts (B,N) int32, shared by the C channels of a cloud, NULL = 'all'   ->   out (B,C,N) f32.
+ * For row (b,c,n) let c_n = min(max(counts[b,n], 1), K) -- the reference's clamp(min=1); a count above K masks nothing.
+ * Slot k < c_n carries s_k, slot k >= c_n carries exactly -1e9f (as the reference and pdr_attention_pool);
+ * w = softmax over the K slots and out = sum_k w_k v_k.  ONE launch, no workspace, no atomics of any kind, no
+ * allocation, no synchronisation: capturable.  Every output element is written exactly once; the same input gives the
+ * same bits.
+ *   - operation chain, one fp32 rounding per step (no fused multiply-add but the one written):
+ *         t_k = k < c_n ? s_k : -1e9f,   a_k = fl(t_k * fl(log2 e)),   m = max_k a_k (exact),
+ *         e_k = v_exp_f32(fl(a_k - m)),  l = sum_k e_k,  acc = sum_k fma(v_k, e_k, acc),  out = fl(acc / l).
+ *     The sums run in ascending k from +0.0f in the scalar family; in the vector family per lane (4 consecutive slots,
+ *     ascending) and then as a butterfly over the row's lanes (lane distance 1, 2, 4, 8).  The two families agree up to
+ *     that order.
+ *   - the score held by a masked slot is NOT inspected.  A deliberate departure from the torch composition, for a
+ *     non-finite masked score only: there scores * mask gives inf * 0 = NaN.  Masked slots of `values` ARE multiplied
+ *     by their weight (0 unless the valid scores are near -1e9), as in the reference: a non-finite masked value gives NaN.
+ *   - two kernel families, chosen on the host and reported by pdr_attention_pool_cf_plan.  Vector: K % 4 == 0 and every
+ *     non-NULL pointer of the call 16-byte aligned; a row belongs to L = ceil_pow2(K / 4) adjacent lanes, one float4
+ *     each (a wave's load covers 64 / L consecutive rows), max / sum / dot folded across them with DPP; 256 / L rows per
+ *     workgroup, the grid covers all rows.  Scalar: any other 1 <= K <= 64, or a misaligned pointer (a contiguous view
+ *     with a storage offset); a thread per row, scalar loads.
+ *   - validation, decided on the host before any launch, in this order: a negative size or K <= 0: PDR_EINVAL;
+ *     B C N == 0: PDR_OK, nothing launched, no pointer looked at; K > 64 or B C N K >= 2^31: PDR_EUNSUPPORTED; a NULL
+ *     scores / values / out: PDR_EINVAL.  Elements are indexed in size_t. */
+int pdr_attention_pool_cf(const float *scores, const float *values, const int *counts,
+                          int B, int C, int N, int K, float *out, pdr_stream_t stream);
+/* Backward of pdr_attention_pool_cf w.r.t. scores and values.  grad_out (B,C,N); grad_scores / grad_values (B,C,N,K),
+ * fully written; either may be NULL (autograd's needs_input_grad), both NULL: PDR_EINVAL.  The kernel recomputes m, l,
+ * e_k and out from scores / values by the forward's operation chain (the forward's bits; no weight tensor and no `out`
+ * is saved or passed), then, every product rounded before it is used,
+ *     rl = fl(1 / l),   w_k = fl(e_k * rl),
+ *     grad_values[k] = fl(g * w_k)
+ *     grad_scores[k] = k < c_n ? fl(fl(g * w_k) * fl(v_k - out)) : +0.0f
+ * ONE launch, no workspace, no atomics of any kind, no allocation, no synchronisation: capturable.  Every output
+ * element is written exactly once; the same input gives the same bits, and asking for one gradient only changes no bit
+ * of it.  Kernel families and alignment rule as the forward (all of scores, values, counts, grad_out and the non-NULL
+ * gradients).  Validation: the forward's size checks and codes in the same order, then a NULL scores / values /
+ * grad_out, or both gradients NULL: PDR_EINVAL. */
+int pdr_attention_pool_cf_grad(const float *scores, const float *values, const int *counts,
+                               const float *grad_out, int B, int C, int N, int K,
+                               float *grad_scores, float *grad_values, pdr_stream_t stream);
+/* Which kernel the two calls above run for K slots per row.  Host only (no HIP call, no device pointer); the launches
+ * read the same decision.  aligned16 != 0: every non-NULL pointer of the call is 16-byte aligned.
+ * out = {family (0 scalar, 1 vector), lanes per row L, rows per workgroup (256 / L), rows per lane group per grid pass
+ * -- 0: the grid covers all rows, which it always does}.  K <= 0 or a NULL out: PDR_EINVAL; K > 64: PDR_EUNSUPPORTED. */
+int pdr_attention_pool_cf_plan(int K, int aligned16, int out[4]);
 /* Voxel-grid occupancy counters of a SET of clouds (the loop of entropy_of_occupancy_grid,
  * pointnet2/models/pvd/metrics/evaluation_metrics.py:198-237, which queries a KD-tree per cloud and counts in Python):
  *     clouds (S,n,3) f32  ->  counters[c] += points of all clouds whose nearest kept grid cell is c,

@@ -47,6 +47,9 @@ SIGNATURES = {
     "pdr_chamfer_loss_workspace_bytes": (_Z, [_I, _I, _I]),
     "pdr_chamfer_loss": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P]),
     "pdr_chamfer_loss_grad": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P]),
+    "pdr_attention_pool_cf_plan": (_I, [_I, _I, _P]),
+    "pdr_attention_pool_cf": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P]),
+    "pdr_attention_pool_cf_grad": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
     "pdr_occupancy_grid": (_I, [_P, _P, _I, _I, _I, _P, _P, _I, _P, _P, _P, _P]),
     "pdr_knn_group": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
     "pdr_knn_plan": (_I, [_I, _I, _I, _I, _I, _I, _P]),

@@ -1,6 +1,9 @@
 """Drop-in for the reference's `pointnet2_ops` package (pointnet2_ops/__init__.py:1-3).
 
 `set_deterministic(True | False | None)` chooses the backward kernels of gather / group / three_interpolate /
-knn_points: order-fixed, atomic, or (None, the default) whatever `torch.are_deterministic_algorithms_enabled()` says."""
+knn_points: order-fixed, atomic, or (None, the default) whatever `torch.are_deterministic_algorithms_enabled()` says.
+`set_fused_attention_pool(True | False)` (default False) makes `AttentionModule` pool with the one-launch
+`pointnet2_utils.attention_pool` and its one-launch backward instead of the torch composition."""
 from . import pointnet2_modules, pointnet2_utils  # noqa: F401
-from ._ext import is_deterministic, set_deterministic  # noqa: F401
+from ._ext import (is_deterministic, is_fused_attention_pool, set_deterministic,  # noqa: F401
+                   set_fused_attention_pool)

@@ -64,6 +64,25 @@ def is_deterministic():
     return _deterministic
 
 
+_fused_attention_pool = False     # set_fused_attention_pool: AttentionModule pools with pdr_attention_pool_cf
+
+
+def set_fused_attention_pool(mode):
+    """Process-wide switch: True = `AttentionModule.forward` pools its fp32 GPU tensors with one `attention_pool` launch
+    (and one backward launch) where the kernel supports the shape; False (the default) = the torch composition, as ever.
+    Returns the previous setting."""
+    global _fused_attention_pool
+    if not isinstance(mode, bool):
+        raise TypeError("set_fused_attention_pool takes True or False, got %r" % (mode,))
+    prev, _fused_attention_pool = _fused_attention_pool, mode
+    return prev
+
+
+def is_fused_attention_pool():
+    """Whether AttentionModule.forward takes the fused pooling kernel right now."""
+    return _fused_attention_pool
+
+
 def _scatter_workspace(B, P, N, device):
     """Scratch of one `*_grad_det` call (pdr_scatter_workspace_bytes), a torch allocation per call."""
     nbytes = _lib.load().pdr_scatter_workspace_bytes(int(B), int(P), int(N))
@@ -433,6 +452,60 @@ def chamfer_loss_sums(x, y, x_lengths=None, y_lengths=None):
     if torch.is_grad_enabled() and (x.requires_grad or y.requires_grad):
         return _ChamferLossSums.apply(x, y, x_lengths, y_lengths)
     return _chamfer_loss_forward(x, y, x_lengths, y_lengths, False)[0]
+
+
+def _req_pool(scores, values, count):
+    """Shapes and dtypes of the attention pool's inputs; returns (B, C, N, K) and the count tensor or None ('all')."""
+    _req(scores, "scores", torch.float32)
+    _req(values, "values", torch.float32)
+    _same_device(scores, values)
+    if scores.dim() != 4 or values.shape != scores.shape:
+        raise RuntimeError("attention_pool: scores and values must both be (B, C, N, K), got %s and %s"
+                           % (tuple(scores.shape), tuple(values.shape)))
+    B, C, N, K = scores.shape
+    if count is None or (isinstance(count, str) and count == 'all'):
+        return (B, C, N, K), None
+    _req(count, "count", torch.int32)
+    _same_device(scores, count)
+    if tuple(count.shape) != (B, N):
+        raise RuntimeError("count must have shape (B, N) = (%d, %d), got %s" % (B, N, tuple(count.shape)))
+    return (B, C, N, K), count
+
+
+def attention_pool_supported(B, C, N, K):
+    """Whether pdr_attention_pool_cf takes a (B, C, N, K) problem (it refuses K > 64 and 2^31 elements or more)."""
+    plan = (_lib._c.c_int * 4)()
+    return _lib.load().pdr_attention_pool_cf_plan(int(K), 1, plan) == _lib.PDR_OK and B * C * N * K < 2 ** 31
+
+
+def attention_pool(scores, values, count):
+    """Masked softmax over the K neighbours and weighted sum of the values, in one launch (pdr_attention_pool_cf):
+    scores, values (B,C,N,K) f32, count (B,N) i32 / None / 'all' -> (B,C,N).  Slots k >= clamp(count, 1, K) carry
+    exactly -1e9 (attention.py:71-77)."""
+    (B, C, N, K), cnt = _req_pool(scores, values, count)
+    out = torch.empty((B, C, N), dtype=torch.float32, device=scores.device)
+    with torch.cuda.device(scores.device):
+        _lib.check(_lib.load().pdr_attention_pool_cf(scores.data_ptr(), values.data_ptr(), _ptr(cnt), B, C, N, K,
+                                                     out.data_ptr(), _stream()), "attention_pool")
+    return out
+
+
+def attention_pool_grad(scores, values, count, grad_out, need_scores=True, need_values=True):
+    """Backward of attention_pool in one launch (pdr_attention_pool_cf_grad): recomputes the weights from scores /
+    values, nothing saved.  grad_out (B,C,N) f32 -> (grad_scores, grad_values), each (B,C,N,K) or None when not
+    needed (at least one must be)."""
+    (B, C, N, K), cnt = _req_pool(scores, values, count)
+    _req(grad_out, "grad_out", torch.float32)
+    _same_device(scores, grad_out)
+    if tuple(grad_out.shape) != (B, C, N):
+        raise RuntimeError("grad_out must have shape (B, C, N) = (%d, %d, %d), got %s" % (B, C, N, tuple(grad_out.shape)))
+    gs = torch.empty_like(scores) if need_scores else None
+    gv = torch.empty_like(values) if need_values else None
+    with torch.cuda.device(scores.device):
+        _lib.check(_lib.load().pdr_attention_pool_cf_grad(scores.data_ptr(), values.data_ptr(), _ptr(cnt),
+                                                          grad_out.data_ptr(), B, C, N, K, _ptr(gs), _ptr(gv),
+                                                          _stream()), "attention_pool_grad")
+    return gs, gv
 
 
 def chamfer_pairwise(x, y, x_lengths=None, y_lengths=None, symmetric=False):

@@ -11,6 +11,9 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from . import _ext
+from .pointnet2_utils import attention_pool
+
 
 class MyGroupNorm(nn.Module):
     """GroupNorm over the first C - C % G channels; trailing channels (appended xyz
@@ -42,6 +45,12 @@ def _act_norm_conv(cin, cout, norm):
     return layers
 
 
+def _fusable(scores, values):
+    """fp32 GPU tensors of a shape pdr_attention_pool_cf takes (K <= 64, fewer than 2^31 elements)."""
+    return scores.is_cuda and values.is_cuda and scores.dtype == torch.float32 and values.dtype == torch.float32 and \
+        _ext.attention_pool_supported(*scores.shape)
+
+
 class AttentionModule(nn.Module):
     def __init__(self, C_in1, C_in2, C1, C2, C_out, attention_bn=True, transform_grouped_feat_out=True,
                  last_activation=True):
@@ -68,6 +77,13 @@ class AttentionModule(nn.Module):
         q = self.feat_conv(feat.unsqueeze(-1)).expand(-1, -1, -1, K)
         k = self.grouped_feat_conv(grouped_feat)
         scores = self.weight_conv(torch.cat([q, k], dim=1))
+        if _ext.is_fused_attention_pool() and _fusable(scores, grouped_feat_out):
+            # one launch forward, one backward, no saved softmax (pdr_attention_pool_cf); the switch is off by default
+            if self.transform_grouped_feat_out:
+                grouped_feat_out = self.feat_out_conv(grouped_feat_out)
+            if not (isinstance(count, str) and count == 'all'):
+                count = count.int().contiguous()
+            return attention_pool(scores.contiguous(), grouped_feat_out.contiguous(), count)
         if not (isinstance(count, str) and count == 'all'):
             mask = count_to_mask(torch.clamp(count, min=1), K).unsqueeze(1).float()
             scores = scores * mask + (-1e9) * (1 - mask)

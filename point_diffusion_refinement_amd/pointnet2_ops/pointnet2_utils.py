@@ -5,6 +5,8 @@ the reference's pointnet2_ops/pointnet2_utils.py, running on libpdr_hip.so.
     grouping_operation, ball_query           (pointnet2_utils.py:93,129,164,219,268,304)
     QueryAndGroup, GroupAll, group_knn       (:307,441,487)
     count_to_mask, average_feature           (:36,46)
+    attention_pool                           (attention.py:71-77 as one op: masked softmax over K and the weighted
+                                              sum of the values, with a one-launch backward that saves no weights)
 
 kNN comes from this package's own `_ext.knn_points` (the reference imports
 pytorch3d.ops.knn, :7).  Autograd: FPS / ball_query / three_nn are
@@ -133,6 +135,33 @@ class GroupingOperation(Function):
 
 
 grouping_operation = GroupingOperation.apply
+
+
+class AttentionPool(Function):
+    """scores, values (B,C,N,K) f32, count (B,N) i32 / None / 'all' -> (B,C,N): _ext.attention_pool; the backward
+    recomputes the softmax from the saved inputs (no weight tensor is kept) and is order-fixed."""
+
+    @staticmethod
+    def forward(ctx, scores, values, count):
+        if isinstance(count, torch.Tensor):
+            ctx.save_for_backward(scores, values, count)
+        else:
+            ctx.save_for_backward(scores, values)
+        return _ext.attention_pool(scores, values, count)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        scores, values = ctx.saved_tensors[:2]
+        count = ctx.saved_tensors[2] if len(ctx.saved_tensors) > 2 else None
+        need_s, need_v = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if not (need_s or need_v):
+            return None, None, None
+        gs, gv = _ext.attention_pool_grad(scores, values, count, grad_out.contiguous().float(), need_s, need_v)
+        return gs, gv, None                                     # count (integer) is not differentiable
+
+
+attention_pool = AttentionPool.apply
 
 
 class BallQuery(Function):
