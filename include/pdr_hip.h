@@ -67,7 +67,9 @@ typedef void *pdr_stream_t; /* hipStream_t */
  *                for the two pooled entry points) is new; pdr_scatter_workspace_bytes and the four deterministic backward
  *                twins pdr_*_grad_det are new; pdr_chamfer_loss_workspace_bytes / pdr_chamfer_loss / pdr_chamfer_loss_grad
  *                are new; pdr_fps_ragged_workspace_bytes / pdr_fps_ragged_plan / pdr_furthest_point_sampling_ragged are
- *                new; pdr_attention_pool_cf_plan / pdr_attention_pool_cf / pdr_attention_pool_cf_grad are new. */
+ *                new; pdr_attention_pool_cf_plan / pdr_attention_pool_cf / pdr_attention_pool_cf_grad are new;
+ *                pdr_group_norm_act_workspace_bytes / pdr_group_norm_act_plan / pdr_group_norm_act /
+ *                pdr_group_norm_act_grad are new. */
 int pdr_version(void);
 /* last hip error string seen by this thread after a PDR_ELAUNCH ("" if none) */
 const char *pdr_last_error(void);
@@ -369,6 +371,57 @@ int pdr_attention_pool_cf_grad(const float *scores, const float *values, const i
  * out = {family (0 scalar, 1 vector), lanes per row L, rows per workgroup (256 / L), rows per lane group per grid pass
  * -- 0: the grid covers all rows, which it always does}.  K <= 0 or a NULL out: PDR_EINVAL; K > 64: PDR_EUNSUPPORTED. */
 int pdr_attention_pool_cf_plan(int K, int aligned16, int out[4]);
+/* MyGroupNorm followed by an activation (pointnet2_ops/attention.py:18-32, pointnet2_modules.py:37-53) for the TRAINABLE
+ * path, as one differentiable op (the inference path folds GroupNorm into its consumer kernels: pdr_gn_fold):
+ *     x (B,C,S) f32, dense, S = the product of all trailing dimensions;  gamma, beta (Cn) f32, both NULL = 1 and 0
+ *     ->  y (B,C,S) f32,  mean, rstd (B,G) f32 (either may be NULL: a caller that needs no gradient).
+ * Cn = C - C % G, Cg = Cn / G.  Group g of cloud b is the contiguous slab of m = Cg S floats at (b C + g Cg) S:
+ *     mean, biased variance, rstd = 1 / sqrt(var + eps);  c < Cn: z = (x - mean) rstd gamma[c] + beta[c];
+ *     c >= Cn (the appended xyz channels): z = x;   y = act(z) on every channel,
+ *     act 0: none, 1: ReLU (z > 0 ? z : +0), 2: Swish (z sigmoid(z)).
+ * TWO launches (statistics partials, then apply), no atomics of any kind, no allocation, no synchronisation:
+ * capturable.  Every output element is written exactly once; the same input gives the same bits, and cloud b of a
+ * batched call has the bits of the B = 1 call on that cloud.
+ *   - operation chain (csrc/group_norm_act.hip states it in full): the moments s1 = sum x, s2 = sum x^2 accumulate in
+ *     double; mean_d = s1 / m, var_d = max(s2 / m - mean_d^2, 0); mean = float(mean_d), rstd = float(1 / sqrt(var_d +
+ *     eps)) are the values written AND applied; then, one fp32 rounding each, d = x - mean, xh = d rstd,
+ *     z = fma(xh, gamma, beta); Swish: t = z fl(-log2 e), e = v_exp_f32(t), s = 1 / (1 + e), y = z s.
+ *   - summation order: a function of (Cg, S) and the kernel family only.  A slab is cut into P <= 32 partitions of E
+ *     elements (E a multiple of 1024, at least 8192, from m alone; pdr_group_norm_act_plan reports both); inside a
+ *     partition thread t of 256 takes elements (256 i + t) V .. + V - 1, i ascending, then a lane butterfly, the four
+ *     waves ascending, the P partials ascending.
+ *   - two kernel families: vector (V = 4: S % 4 == 0 and x, y 16-byte aligned) and scalar (V = 1: anything else, such
+ *     as a contiguous view with a storage offset).  They agree up to the summation order.
+ *   - workspace: pdr_group_norm_act_workspace_bytes(B, C, S, G) bytes, 8-byte aligned, the caller's; it serves either
+ *     call (forward: B G P pairs of doubles; backward: B C pairs).  Not read after the call returns its last kernel.
+ *   - validation, decided on the host before any launch, in this order: B, C or S negative, G <= 0, act outside 0..2,
+ *     eps negative or NaN: PDR_EINVAL; 0 < C < G (Cn == 0): PDR_EINVAL; B C S == 0: PDR_OK, nothing launched, no
+ *     pointer looked at; B C S >= 2^31: PDR_EUNSUPPORTED; a NULL x / y / workspace, or exactly one of gamma / beta
+ *     NULL: PDR_EINVAL. */
+int pdr_group_norm_act(const float *x, const float *gamma, const float *beta, int B, int C, long S, int G,
+                       float eps, int act, float *y, float *mean, float *rstd, void *workspace, pdr_stream_t stream);
+/* Backward of pdr_group_norm_act.  mean, rstd: what the forward wrote; grad_y (B,C,S); grad_x (B,C,S), grad_gamma,
+ * grad_beta (Cn), each fully written, each may be NULL (autograd's needs_input_grad), all three NULL: PDR_EINVAL;
+ * gamma NULL with a non-NULL grad_gamma / grad_beta: PDR_EINVAL.  Nothing but x and the (B,G) statistics is saved: the
+ * kernels recompute d, xh, z (and the sigmoid) from x, mean, rstd, gamma, beta by the forward's operation sequence --
+ * the forward's bits, so the ReLU mask is the forward's -- then
+ *     dz = dy act'(z)      (ReLU: z > 0 ? dy : +0;  Swish: dy (s (1 + z (1 - s))), every product rounded)
+ *     r1[b,c] = sum_s dz xh,  r2[b,c] = sum_s dz            in double, to the workspace, order as a partition's
+ *     c1 = sum_c gamma r1,  c2 = sum_c gamma r2             over the slab's Cg rows, ascending, in double
+ *     dx = rstd (gamma dz - fma(xh, float(c1 / m), float(c2 / m)));   pass-through channel: dx = dz
+ *     dgamma[c] = sum_b r1[b,c],  dbeta[c] = sum_b r2[b,c]  ascending b, in double, rounded once
+ * THREE launches (row sums, dx, parameter sums; dx or the parameter sums are skipped when not asked for), no atomics,
+ * no allocation, no synchronisation: capturable; the same input gives the same bits.  Kernel families as the forward
+ * (x, grad_y and grad_x aligned).  Validation: the forward's size checks in the same order, then the pointers. */
+int pdr_group_norm_act_grad(const float *x, const float *gamma, const float *beta, const float *mean,
+                            const float *rstd, const float *grad_y, int B, int C, long S, int G, int act,
+                            float *grad_x, float *grad_gamma, float *grad_beta, void *workspace, pdr_stream_t stream);
+/* Bytes of workspace either call above needs; 0 for an empty or invalid problem.  Host only. */
+size_t pdr_group_norm_act_workspace_bytes(int B, int C, long S, int G);
+/* The decision the two calls above read.  Host only.  aligned16 != 0: the tensor pointers of the call are 16-byte
+ * aligned.  out = {family (0 scalar, 1 vector), partitions per slab P, elements per partition E, Cg}.
+ * C, S or G <= 0, C < G or a NULL out: PDR_EINVAL; C S >= 2^31: PDR_EUNSUPPORTED. */
+int pdr_group_norm_act_plan(int C, long S, int G, int aligned16, long out[4]);
 /* Voxel-grid occupancy counters of a SET of clouds (the loop of entropy_of_occupancy_grid,
  * pointnet2/models/pvd/metrics/evaluation_metrics.py:198-237, which queries a KD-tree per cloud and counts in Python):
  *     clouds (S,n,3) f32  ->  counters[c] += points of all clouds whose nearest kept grid cell is c,

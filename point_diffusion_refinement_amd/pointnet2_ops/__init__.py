@@ -3,7 +3,9 @@
 `set_deterministic(True | False | None)` chooses the backward kernels of gather / group / three_interpolate /
 knn_points: order-fixed, atomic, or (None, the default) whatever `torch.are_deterministic_algorithms_enabled()` says.
 `set_fused_attention_pool(True | False)` (default False) makes `AttentionModule` pool with the one-launch
-`pointnet2_utils.attention_pool` and its one-launch backward instead of the torch composition."""
+`pointnet2_utils.attention_pool` and its one-launch backward instead of the torch composition.
+`set_fused_group_norm(True | False)` (default False) makes every `MyGroupNorm` of the module path, with the ReLU / Swish
+that follows it, run as the one op `pointnet2_utils.group_norm_act` instead of nn.GroupNorm, cat and activation."""
 from . import pointnet2_modules, pointnet2_utils  # noqa: F401
-from ._ext import (is_deterministic, is_fused_attention_pool, set_deterministic,  # noqa: F401
-                   set_fused_attention_pool)
+from ._ext import (is_deterministic, is_fused_attention_pool, is_fused_group_norm, set_deterministic,  # noqa: F401
+                   set_fused_attention_pool, set_fused_group_norm)

@@ -83,6 +83,26 @@ def is_fused_attention_pool():
     return _fused_attention_pool
 
 
+_fused_group_norm = False         # set_fused_group_norm: MyGroupNorm (+ the activation after it) runs pdr_group_norm_act
+
+
+def set_fused_group_norm(mode):
+    """Process-wide switch: True = every `MyGroupNorm` of the module path, with the ReLU / Swish that directly follows
+    it in the same `nn.Sequential`, runs as one `group_norm_act` op (and its backward) for fp32 GPU tensors of a shape
+    the kernels support; False (the default) = `nn.GroupNorm`, the slice-and-cat and the activation modules, as ever.
+    Returns the previous setting."""
+    global _fused_group_norm
+    if not isinstance(mode, bool):
+        raise TypeError("set_fused_group_norm takes True or False, got %r" % (mode,))
+    prev, _fused_group_norm = _fused_group_norm, mode
+    return prev
+
+
+def is_fused_group_norm():
+    """Whether MyGroupNorm takes the fused kernels right now."""
+    return _fused_group_norm
+
+
 def _scatter_workspace(B, P, N, device):
     """Scratch of one `*_grad_det` call (pdr_scatter_workspace_bytes), a torch allocation per call."""
     nbytes = _lib.load().pdr_scatter_workspace_bytes(int(B), int(P), int(N))
@@ -506,6 +526,90 @@ def attention_pool_grad(scores, values, count, grad_out, need_scores=True, need_
                                                           grad_out.data_ptr(), B, C, N, K, _ptr(gs), _ptr(gv),
                                                           _stream()), "attention_pool_grad")
     return gs, gv
+
+
+GROUP_NORM_ACTS = ("none", "relu", "swish")      # the `act` codes 0, 1, 2 of pdr_group_norm_act
+
+
+def _req_group_norm(x, weight, bias, num_groups, act):
+    """Shapes and dtypes of group_norm_act's inputs; returns (B, C, S, G, act code)."""
+    _req(x, "x", torch.float32)
+    if x.dim() < 2:
+        raise RuntimeError("group_norm_act: x must be (B, C, ...), got %s" % (tuple(x.shape),))
+    if act not in GROUP_NORM_ACTS:
+        raise ValueError("group_norm_act: act must be one of %s, got %r" % (GROUP_NORM_ACTS, act))
+    B, C, G = int(x.shape[0]), int(x.shape[1]), int(num_groups)
+    S = 1
+    for d in x.shape[2:]:
+        S *= int(d)
+    if (weight is None) != (bias is None):
+        raise RuntimeError("group_norm_act: weight and bias must both be given or both be None")
+    if weight is not None:
+        cn = C - C % G if G > 0 else -1
+        for t, name in ((weight, "weight"), (bias, "bias")):
+            _req(t, name, torch.float32)
+            _same_device(x, t)
+            if tuple(t.shape) != (cn,):
+                raise RuntimeError("%s must have shape (C - C %% G,) = (%d,), got %s" % (name, cn, tuple(t.shape)))
+    return B, C, S, G, GROUP_NORM_ACTS.index(act)
+
+
+def _group_norm_workspace(B, C, S, G, device):
+    nbytes = _lib.load().pdr_group_norm_act_workspace_bytes(B, C, S, G)
+    return torch.empty(max(nbytes // 8, 1), dtype=torch.float64, device=device)
+
+
+def group_norm_act_supported(shape, num_groups):
+    """Whether pdr_group_norm_act takes an x of this shape (B, C, ...): at least `num_groups` channels, fewer than 2^31
+    elements."""
+    if len(shape) < 2:
+        return False
+    n = 1
+    for d in shape:
+        n *= int(d)
+    return 0 < int(num_groups) <= int(shape[1]) and n < 2 ** 31
+
+
+def group_norm_act(x, weight, bias, num_groups, eps=1e-5, act="none"):
+    """act(MyGroupNorm(x)) in two launches (pdr_group_norm_act): x (B, C, ...) f32, weight / bias (C - C % G) f32 or
+    both None -> (y like x, mean (B, G), rstd (B, G)).  Channels past C - C % G are not normalised; the activation
+    ('none' | 'relu' | 'swish') applies to all."""
+    B, C, S, G, code = _req_group_norm(x, weight, bias, num_groups, act)
+    y = torch.empty_like(x)
+    mean = torch.empty((B, max(G, 0)), dtype=torch.float32, device=x.device)
+    rstd = torch.empty_like(mean)
+    ws = _group_norm_workspace(B, C, S, G, x.device)
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.load().pdr_group_norm_act(x.data_ptr(), _ptr(weight), _ptr(bias), B, C, S, G, float(eps), code,
+                                                  y.data_ptr(), mean.data_ptr(), rstd.data_ptr(), ws.data_ptr(),
+                                                  _stream()), "group_norm_act")
+    return y, mean, rstd
+
+
+def group_norm_act_grad(x, weight, bias, mean, rstd, grad_y, num_groups, act="none", need_x=True, need_weight=True,
+                        need_bias=True):
+    """Backward of group_norm_act in three launches (pdr_group_norm_act_grad): recomputes z from x and the saved (B, G)
+    statistics.  -> (grad_x, grad_weight, grad_bias), None where not needed (at least one must be; without weight /
+    bias the last two are always None)."""
+    B, C, S, G, code = _req_group_norm(x, weight, bias, num_groups, act)
+    _req(grad_y, "grad_y", torch.float32)
+    if grad_y.shape != x.shape:
+        raise RuntimeError("grad_y must have x's shape %s, got %s" % (tuple(x.shape), tuple(grad_y.shape)))
+    for t, name in ((mean, "mean"), (rstd, "rstd")):
+        _req(t, name, torch.float32)
+        if tuple(t.shape) != (B, G):
+            raise RuntimeError("%s must have shape (B, G) = (%d, %d), got %s" % (name, B, G, tuple(t.shape)))
+    _same_device(x, grad_y, mean, rstd)
+    gx = torch.empty_like(x) if need_x else None
+    gw = torch.empty_like(weight) if need_weight and weight is not None else None
+    gb = torch.empty_like(bias) if need_bias and bias is not None else None
+    ws = _group_norm_workspace(B, C, S, G, x.device)
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.load().pdr_group_norm_act_grad(x.data_ptr(), _ptr(weight), _ptr(bias), mean.data_ptr(),
+                                                       rstd.data_ptr(), grad_y.data_ptr(), B, C, S, G, code, _ptr(gx),
+                                                       _ptr(gw), _ptr(gb), ws.data_ptr(), _stream()),
+                   "group_norm_act_grad")
+    return gx, gw, gb
 
 
 def chamfer_pairwise(x, y, x_lengths=None, y_lengths=None, symmetric=False):

@@ -12,7 +12,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _ext
-from .pointnet2_utils import attention_pool
+from .pointnet2_utils import attention_pool, group_norm_act
 
 
 class MyGroupNorm(nn.Module):
@@ -26,10 +26,53 @@ class MyGroupNorm(nn.Module):
         self.group_norm = nn.GroupNorm(self.num_groups, self.num_channels)
 
     def forward(self, x):
+        if self.fusable(x):
+            return self.fused(x, 'none')
         c = self.num_channels
         if x.shape[1] == c:
             return self.group_norm(x)
         return torch.cat([self.group_norm(x[:, :c]), x[:, c:]], dim=1)
+
+    def fusable(self, x):
+        """The switch is on (`set_fused_group_norm`, default off) and x is an fp32 GPU tensor of a shape
+        pdr_group_norm_act takes."""
+        return _ext.is_fused_group_norm() and x.is_cuda and x.dtype == torch.float32 and \
+            x.shape[1] - x.shape[1] % self.num_groups == self.num_channels and \
+            _ext.group_norm_act_supported(x.shape, self.num_groups)
+
+    def fused(self, x, act):
+        """act(self(x)) as one op: two launches forward, three backward, only x and (B, G) statistics saved."""
+        gn = self.group_norm
+        return group_norm_act(x, gn.weight, gn.bias, self.num_groups, gn.eps, act)
+
+
+def fused_act_of(module):
+    """'relu' / 'swish' for an activation module group_norm_act can absorb, else None."""
+    if isinstance(module, nn.ReLU):
+        return 'relu'
+    return getattr(module, 'fused_act', None)
+
+
+class NormActSequential(nn.Sequential):
+    """nn.Sequential (same children, same parameter names) whose forward, with `set_fused_group_norm(True)`, runs a
+    MyGroupNorm and the activation module directly after it as one `group_norm_act` call.  With the switch off it
+    calls its children in order, as nn.Sequential does."""
+
+    def forward(self, x):
+        if not _ext.is_fused_group_norm():
+            return super().forward(x)
+        mods = list(self)
+        i = 0
+        while i < len(mods):
+            m = mods[i]
+            if isinstance(m, MyGroupNorm) and m.fusable(x):
+                act = fused_act_of(mods[i + 1]) if i + 1 < len(mods) else None
+                x = m.fused(x, act or 'none')
+                i += 2 if act else 1
+            else:
+                x = m(x)
+                i += 1
+        return x
 
 
 def count_to_mask(count, K):
@@ -59,7 +102,7 @@ class AttentionModule(nn.Module):
         self.feat_conv = nn.Conv2d(C_in1, C1, kernel_size=1)
         self.grouped_feat_conv = nn.Conv2d(C_in2, C2, kernel_size=1)
         inter = min(C1 + C2, C_out)
-        self.weight_conv = nn.Sequential(*(_act_norm_conv(C1 + C2, inter, attention_bn) +
+        self.weight_conv = NormActSequential(*(_act_norm_conv(C1 + C2, inter, attention_bn) +
                                            _act_norm_conv(inter, C_out, attention_bn)))
         self.transform_grouped_feat_out = transform_grouped_feat_out
         if transform_grouped_feat_out:
@@ -68,7 +111,7 @@ class AttentionModule(nn.Module):
                 if attention_bn:
                     tail.append(MyGroupNorm(min(32, C_out), C_out))
                 tail.append(nn.ReLU(inplace=True))
-            self.feat_out_conv = nn.Sequential(*tail)
+            self.feat_out_conv = NormActSequential(*tail)
 
     def forward(self, feat, grouped_feat, grouped_feat_out, count):
         """feat (B,C_in1,N) query; grouped_feat (B,C_in2,N,K) key; grouped_feat_out (B,C_out,N,K)

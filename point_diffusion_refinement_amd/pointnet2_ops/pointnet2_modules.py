@@ -14,7 +14,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import pointnet2_utils
-from .attention import AttentionModule, MyGroupNorm
+from .attention import AttentionModule, MyGroupNorm, NormActSequential
 
 
 def swish(x):
@@ -22,6 +22,8 @@ def swish(x):
 
 
 class Swish(nn.Module):
+    fused_act = 'swish'          # what NormActSequential folds into the MyGroupNorm before it
+
     def forward(self, x):
         return swish(x)
 
@@ -50,7 +52,7 @@ def build_shared_mlp(mlp_spec, bn=True, bn_first=False, bias=False, activation='
             if bn:
                 layers.append(MyGroupNorm(32, cout))
             layers.append(_activation(activation))
-    return nn.Sequential(*layers)
+    return NormActSequential(*layers)
 
 
 def _xyz_channels(use_xyz, include_abs, include_center):

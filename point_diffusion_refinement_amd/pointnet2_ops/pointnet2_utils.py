@@ -164,6 +164,41 @@ class AttentionPool(Function):
 attention_pool = AttentionPool.apply
 
 
+class GroupNormAct(Function):
+    """act(MyGroupNorm(x)): _ext.group_norm_act.  Saves x, weight, bias and the (B, G) mean / rstd -- never y; the
+    backward recomputes the normalised values from them and is order-fixed."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, num_groups, eps, act):
+        y, mean, rstd = _ext.group_norm_act(x, weight, bias, num_groups, eps, act)
+        ctx.num_groups, ctx.act, ctx.affine = num_groups, act, weight is not None
+        if ctx.affine:
+            ctx.save_for_backward(x, mean, rstd, weight, bias)
+        else:
+            ctx.save_for_backward(x, mean, rstd)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_y):
+        x, mean, rstd = ctx.saved_tensors[:3]
+        weight, bias = ctx.saved_tensors[3:] if ctx.affine else (None, None)
+        need_x = ctx.needs_input_grad[0]
+        need_w, need_b = (ctx.needs_input_grad[1], ctx.needs_input_grad[2]) if ctx.affine else (False, False)
+        if not (need_x or need_w or need_b):
+            return None, None, None, None, None, None
+        gx, gw, gb = _ext.group_norm_act_grad(x, weight, bias, mean, rstd, grad_y.contiguous().float(), ctx.num_groups,
+                                              ctx.act, need_x, need_w, need_b)
+        return gx, gw, gb, None, None, None
+
+
+def group_norm_act(x, weight, bias, num_groups, eps=1e-5, act='none'):
+    """x (B, C, ...) f32 on the GPU, weight / bias (C - C % num_groups) or both None -> act(MyGroupNorm(x)) as one
+    differentiable op (pdr_group_norm_act / pdr_group_norm_act_grad); act 'none' | 'relu' | 'swish'.  The trailing
+    C % num_groups channels are not normalised, the activation applies to every channel (attention.py:18-32)."""
+    return GroupNormAct.apply(x.contiguous(), weight, bias, num_groups, eps, act)
+
+
 class BallQuery(Function):
     @staticmethod
     def forward(ctx, radius, nsample, xyz, new_xyz):
