@@ -17,11 +17,16 @@
 // with tierank = bitrev(k % R) * ceil(N/R) + k / R and R = opt_n_threads(N)
 // (cuda_utils.h:13-19).  Each thread pre-sorts its points by tierank so the
 // in-register scan needs only the reference's strict '>'.
-#include "pdr_common.h"
+//
+// The pieces of a round that do not depend on a kernel's slot layout (exclusion rule, packed distance update, DPP wave
+// arg-max, cross-wave exchange, the sorted load, the stream form) are in fps_round.h, shared with fps_ragged.hip.
+#include "fps_round.h"
 
 #include <cstdlib>
 
 namespace {
+
+using fps::f2;
 
 constexpr int kMaxResidentN = 16384;  // 16-bit k / tierank fields
 
@@ -51,41 +56,7 @@ __global__ __launch_bounds__(T) void fps_resident_kernel(
 
   float px[PPT], py[PPT], pz[PPT], tmp[PPT];
   unsigned low[PPT];  // (0xFFFF - tierank) << 16 | k ; larger = preferred
-#pragma unroll
-  for (int i = 0; i < PPT; ++i) {
-    const int k = tid + i * T;
-    if (k < N) {
-      px[i] = p[k * 3 + 0];
-      py[i] = p[k * 3 + 1];
-      pz[i] = p[k * 3 + 2];
-      const float mag = PDR_SUM3(px[i], py[i], pz[i]);
-      // reference: `if (mag <= 1e-3) continue;` -- float promoted to double
-      tmp[i] = (static_cast<double>(mag) <= 1e-3) ? -1.0f : 1e10f;
-      const unsigned rank = pdr::bitrev(static_cast<unsigned>(k % R), Rbits) * Q + k / R;
-      low[i] = ((0xFFFFu - rank) << 16) | static_cast<unsigned>(k);
-    } else {
-      px[i] = py[i] = pz[i] = 0.0f;
-      tmp[i] = -1.0f;  // padding: never selectable, never updated upward
-      low[i] = 0u;
-    }
-  }
-  // sort this thread's points by descending `low` (= ascending tierank) so that
-  // "first strictly greater wins" inside the thread equals the reference order.
-#pragma unroll
-  for (int a = 0; a < PPT - 1; ++a) {
-#pragma unroll
-    for (int c = 0; c < PPT - 1 - a; ++c) {
-      if (low[c] < low[c + 1]) {
-        float t;
-        unsigned u;
-        t = px[c]; px[c] = px[c + 1]; px[c + 1] = t;
-        t = py[c]; py[c] = py[c + 1]; py[c + 1] = t;
-        t = pz[c]; pz[c] = pz[c + 1]; pz[c + 1] = t;
-        t = tmp[c]; tmp[c] = tmp[c + 1]; tmp[c + 1] = t;
-        u = low[c]; low[c] = low[c + 1]; low[c + 1] = u;
-      }
-    }
-  }
+  FPS_LOAD_SORTED_SLOTS(T, PPT, p, N, R, Rbits, Q, tid, px, py, pz, tmp, low)
 
   if (tid == 0) out[0] = 0;
   __syncthreads();
@@ -109,18 +80,7 @@ __global__ __launch_bounds__(T) void fps_resident_kernel(
     unsigned long long key =
         best < 0.0f ? 0ull : pdr::u64_from(__float_as_uint(best), bestlow);
     key = pdr::wave_max_u64(key);
-    if constexpr (W > 1) {
-      unsigned long long* s = slots + (j & 1) * W;
-      if ((tid & 63) == 0) s[tid >> 6] = key;
-      __syncthreads();
-      unsigned long long r = s[0];
-#pragma unroll
-      for (int w = 1; w < W; ++w) {
-        const unsigned long long o = s[w];
-        r = o > r ? o : r;
-      }
-      key = r;
-    }
+    key = fps::exchange_max<W>(slots + (j & 1) * W, key);
     old = static_cast<int>(key & 0xFFFFull);
     if (tid == 0) out[j] = old;
   }
@@ -129,13 +89,11 @@ __global__ __launch_bounds__(T) void fps_resident_kernel(
 // One WAVE per cloud (N <= 64 * PPT <= 2048): no workgroup barrier and no LDS exchange in the round.
 //   * lane l, slot i owns the point of tie rank r = 64 i + l (k = (r % Q) R + bitrev(r / Q)): inside a lane the
 //     slots are already in the reference's tie order, so "first strictly greater wins" needs no sorting;
-//   * the distance update runs on PACKED fp32 (two points per v_pk_* instruction, each half IEEE-exact, the same
-//     SUM3 expression tree -> identical bits);
+//   * the distance update runs on PACKED fp32 (FPS_PACKED_UPDATE);
 //   * the wave arg-max is two 32-bit DPP reductions (value, then rank|index among the lanes holding the value)
 //     instead of one on a 64-bit key; the winner's coordinates come back from LDS by index (one ds_read_b128).
 // A round is ~7 VALU slots per point + ~150 cycles: 2048 -> 1024 in ~0.26 ms (the 4-wave form needs 0.49 ms
 // because every round ends in a barrier + LDS exchange); the deeper levels of the chain shrink likewise.
-typedef float fps_f2 __attribute__((ext_vector_type(2)));
 
 // (da, la) <- (db > da) ? (db, lb) : (da, la)
 __device__ __forceinline__ void fps_combine(float& da, unsigned& la, float db, unsigned lb) {
@@ -167,7 +125,7 @@ __device__ __forceinline__ void fps_combine2(float& da, unsigned& la, float db, 
 
 // first tree level on two slot pairs (2H, 2H+1) and (2H+2, 2H+3): the slot numbers are immediates
 template <int H>
-__device__ __forceinline__ void fps_first2(const fps_f2& a, const fps_f2& b, float& bd0, unsigned& bs0, float& bd1,
+__device__ __forceinline__ void fps_first2(const f2& a, const f2& b, float& bd0, unsigned& bs0, float& bd1,
                                            unsigned& bs1) {
   unsigned long long m;
   asm volatile(
@@ -183,7 +141,7 @@ __device__ __forceinline__ void fps_first2(const fps_f2& a, const fps_f2& b, flo
       : "vcc");
 }
 template <int H>
-__device__ __forceinline__ void fps_first1(const fps_f2& a, float& bd0, unsigned& bs0) {
+__device__ __forceinline__ void fps_first1(const f2& a, float& bd0, unsigned& bs0) {
   asm volatile(
       "v_cmp_gt_f32 vcc, %3, %2\n\t"
       "s_nop 1\n\t"
@@ -194,7 +152,7 @@ __device__ __forceinline__ void fps_first1(const fps_f2& a, float& bd0, unsigned
       : "vcc");
 }
 template <int H, int NH>
-__device__ __forceinline__ void fps_level0(const fps_f2 (&tmp)[NH], float (&bd)[NH], unsigned (&bs)[NH]) {
+__device__ __forceinline__ void fps_level0(const f2 (&tmp)[NH], float (&bd)[NH], unsigned (&bs)[NH]) {
   if constexpr (H + 1 < NH) {
     fps_first2<H>(tmp[H], tmp[H + 1], bd[H], bs[H], bd[H + 1], bs[H + 1]);
     fps_level0<H + 2, NH>(tmp, bd, bs);
@@ -219,7 +177,7 @@ __global__ __launch_bounds__(T) void fps_wave_kernel(const float* __restrict__ x
   // slot i of thread l holds the point of tie rank r = T i + l; only coordinates and running distances stay in
   // registers -- the slot number is an immediate in the arg-max tree and the point index is recovered from the
   // winning rank with scalar arithmetic once per round
-  fps_f2 px[PPT / 2], py[PPT / 2], pz[PPT / 2], tmp[PPT / 2];
+  f2 px[PPT / 2], py[PPT / 2], pz[PPT / 2], tmp[PPT / 2];
 #pragma unroll
   for (int i = 0; i < PPT; ++i) {
     const int r = i * T + lane;
@@ -229,12 +187,10 @@ __global__ __launch_bounds__(T) void fps_wave_kernel(const float* __restrict__ x
     const int kk = valid ? k : 0;
     const float x = p[kk * 3 + 0], y = p[kk * 3 + 1], z = p[kk * 3 + 2];
     const float mag = PDR_SUM3(x, y, z);
-    // reference: `if (mag <= 1e-3) continue;` -- float promoted to double
-    const float t0 = (!valid || static_cast<double>(mag) <= 1e-3) ? -1.0f : 1e10f;
     px[i >> 1][i & 1] = valid ? x : 0.0f;
     py[i >> 1][i & 1] = valid ? y : 0.0f;
     pz[i >> 1][i & 1] = valid ? z : 0.0f;
-    tmp[i >> 1][i & 1] = t0;                           // padding: never selectable, never updated upward
+    tmp[i >> 1][i & 1] = FPS_INITIAL_DISTANCE(mag, !valid);   // padding: never selectable, never updated upward
   }
   if (lane == 0) out[0] = 0;
   __syncthreads();
@@ -242,34 +198,8 @@ __global__ __launch_bounds__(T) void fps_wave_kernel(const float* __restrict__ x
   int old = 0;
   for (int j = 1; j < m; ++j) {
     const float4 c = cloud4[old];
-    // ---- phase 1: all distance updates (the results ARE the new running minima).  Written stage by stage over
-    // groups of G pairs so that consecutive instructions are independent: one wave per SIMD has nothing else to
-    // hide the VALU latency of a dependent chain behind
-    constexpr int G = (PPT / 2) < 8 ? (PPT / 2) : 8;
-#pragma unroll
-    for (int h0 = 0; h0 < PPT / 2; h0 += G) {
-      fps_f2 dx[G], dy[G], dz[G], d[G];
-#pragma unroll
-      for (int g = 0; g < G; ++g) dy[g] = py[h0 + g] - c.y;
-#pragma unroll
-      for (int g = 0; g < G; ++g) dx[g] = px[h0 + g] - c.x;
-#pragma unroll
-      for (int g = 0; g < G; ++g) d[g] = dy[g] * dy[g];        // PDR_SUM3: fma(c, c, fma(a, a, b * b))
-#pragma unroll
-      for (int g = 0; g < G; ++g) dz[g] = pz[h0 + g] - c.z;
-#pragma unroll
-      for (int g = 0; g < G; ++g) d[g] = __builtin_elementwise_fma(dx[g], dx[g], d[g]);
-#pragma unroll
-      for (int g = 0; g < G; ++g) d[g] = __builtin_elementwise_fma(dz[g], dz[g], d[g]);
-#pragma unroll
-      for (int g = 0; g < G; ++g) {
-        // v_min_f32 directly (fminf / elementwise_min first canonicalise both operands: +1 VALU per point)
-        fps_f2 r;
-        asm("v_min_f32 %0, %1, %2" : "=v"(r[0]) : "v"(d[g][0]), "v"(tmp[h0 + g][0]));
-        asm("v_min_f32 %0, %1, %2" : "=v"(r[1]) : "v"(d[g][1]), "v"(tmp[h0 + g][1]));
-        tmp[h0 + g] = r;
-      }
-    }
+    // ---- phase 1: all distance updates (the results ARE the new running minima), in groups of at most 8 pairs
+    FPS_PACKED_UPDATE(PPT / 2, (PPT / 2 < 8 ? PPT / 2 : 8), px, py, pz, tmp, c.x, c.y, c.z)
     // ---- phase 2: this lane's arg-max as a TREE over its slots: combine(a, b) with a before b in slot order lets b
     // win only if STRICTLY greater = "first maximum in slot order", what the sequential strict-'>' scan returns.
     // The combines are spelled in assembly, two per block (one mask in VCC, one in an SGPR pair, each consumed >= 2
@@ -288,39 +218,21 @@ __global__ __launch_bounds__(T) void fps_wave_kernel(const float* __restrict__ x
       }
     }
     const float best = bd[0];
-    // value first (non-negative floats order like their bit patterns; "no candidate" (-1) -> 0), then the tie rank
-    // among the lanes that hold the winning value: smaller rank preferred -> reduce 0xFFFF - r with max
+    // fps::wave_argmax with the builtin reduction of pdr_common.h: value first, then the tie rank among the lanes that
+    // hold the winning value: smaller rank preferred -> reduce 0xFFFF - r with max
     const unsigned vb = best < 0.0f ? 0u : __float_as_uint(best);
     const unsigned vmax = pdr::wave_max_u32(vb);
     const unsigned rk = 0xFFFFu - (bs[0] * static_cast<unsigned>(T) + static_cast<unsigned>(lane));
     const unsigned cand = (vb == vmax && best >= 0.0f) ? rk : 0u;
     unsigned win = pdr::wave_max_u32(cand);            // uniform in the wave
-    if constexpr (W > 1) {
-      // one barrier per round: every wave publishes (value, rank); all read the W entries back
-      unsigned long long* sl = slots[j & 1];
-      if ((lane & 63) == 0) sl[lane >> 6] = pdr::u64_from(vmax, win);
-      __syncthreads();
-      unsigned long long key = sl[0];
-#pragma unroll
-      for (int w = 1; w < W; ++w) {
-        const unsigned long long o = sl[w];
-        key = o > key ? o : key;
-      }
-      win = static_cast<unsigned>(key & 0xFFFFFFFFull);
-    }
+    // one barrier per round: every wave publishes (value, rank); all read the W entries back
+    win = static_cast<unsigned>(fps::exchange_max<W>(slots[j & 1], pdr::u64_from(vmax, win)) & 0xFFFFFFFFull);
     // rank -> point index with scalar arithmetic (win == 0: no candidate at all -> index 0, as the reference)
     const int rw = 0xFFFF - static_cast<int>(win);
     const int hw = rw / Q, lw = rw - hw * Q;
     old = win == 0u ? 0 : lw * R + static_cast<int>(pdr::bitrev(static_cast<unsigned>(hw), Rbits));
     if (lane == 0) out[j] = old;
   }
-}
-
-template <int T, int PPT>
-int launch_wave(const float* xyz, int B, int N, int m, int R, int Rbits, int Q, int* idx, hipStream_t s) {
-  hipLaunchKernelGGL((fps_wave_kernel<T, PPT>), dim3(B), dim3(T), static_cast<size_t>(N) * sizeof(float4), s, xyz, N,
-                     m, R, Rbits, Q, idx);
-  return pdr::check_launch();
 }
 
 // ---- the resident kernel, instruction-lean (round 5) ------------------------------------------------------------
@@ -333,34 +245,12 @@ int launch_wave(const float* xyz, int B, int N, int m, int R, int Rbits, int Q, 
 // (distance bits, tie key | index) key -- no division -- and removes the rest:
 //   * the cloud lives in LDS as float4: one ds_read_b128 for the last pick instead of an address computation and
 //     three ds_read_b32;
-//   * distance updates on packed fp32 (two points per v_pk_add / v_pk_mul / v_pk_fma: each half IEEE-exact, the same
-//     SUM3 tree -> the same bits), v_min_f32 spelled directly: 32 instructions for eight points instead of 72;
-//   * the wave arg-max as two 32-bit reductions whose DPP shift is an operand modifier of the v_max_u32 itself (one
-//     instruction per step): the value (non-negative floats order like their bit patterns), then the key among the
-//     lanes that hold it: 12 + 6 instructions instead of 47.
+//   * distance updates on packed fp32 (FPS_PACKED_UPDATE: two points per v_pk_add / v_pk_mul / v_pk_fma, v_min_f32
+//     spelled directly): 32 instructions for eight points instead of 72;
+//   * the wave arg-max as two 32-bit reductions whose DPP shift is an operand modifier of the v_max_u32 itself
+//     (fps::wave_argmax): 12 + 6 instructions instead of 47.
 // Same picks as fps_resident_kernel for every input (tests/test_ops_gpu.py::test_fps_index_exact runs both:
 // option fps_lean = 0 selects the old kernel).
-__device__ __forceinline__ unsigned fps_wave_max_u32(unsigned v) {
-  // lanes without a DPP source are disabled for that step and keep their own value; lane 63 ends with the maximum.
-  // (two wait states between a VALU write of a register and a DPP read of it: the assembler does not insert them)
-  asm volatile(
-      "s_nop 1\n\t"
-      "v_max_u32_dpp %0, %0, %0 row_shr:1 row_mask:0xf bank_mask:0xf\n\t"
-      "s_nop 1\n\t"
-      "v_max_u32_dpp %0, %0, %0 row_shr:2 row_mask:0xf bank_mask:0xf\n\t"
-      "s_nop 1\n\t"
-      "v_max_u32_dpp %0, %0, %0 row_shr:4 row_mask:0xf bank_mask:0xf\n\t"
-      "s_nop 1\n\t"
-      "v_max_u32_dpp %0, %0, %0 row_shr:8 row_mask:0xf bank_mask:0xf\n\t"
-      "s_nop 1\n\t"
-      "v_max_u32_dpp %0, %0, %0 row_bcast:15 row_mask:0xa bank_mask:0xf\n\t"
-      "s_nop 1\n\t"
-      "v_max_u32_dpp %0, %0, %0 row_bcast:31 row_mask:0xc bank_mask:0xf\n\t"
-      "s_nop 1"
-      : "+v"(v));
-  return __builtin_amdgcn_readlane(v, 63);
-}
-
 template <int T, int PPT>
 __global__ __launch_bounds__(T) void fps_lean_kernel(const float* __restrict__ xyz, int N, int m, int R, int Rbits,
                                                      int Q, int* __restrict__ idxs) {
@@ -376,42 +266,8 @@ __global__ __launch_bounds__(T) void fps_lean_kernel(const float* __restrict__ x
 
   float sx[PPT], sy[PPT], sz[PPT], st[PPT];
   unsigned low[PPT];  // (0xFFFF - tierank) << 16 | k ; larger = preferred
-#pragma unroll
-  for (int i = 0; i < PPT; ++i) {
-    const int k = tid + i * T;
-    if (k < N) {
-      sx[i] = p[k * 3 + 0];
-      sy[i] = p[k * 3 + 1];
-      sz[i] = p[k * 3 + 2];
-      const float mag = PDR_SUM3(sx[i], sy[i], sz[i]);
-      // reference: `if (mag <= 1e-3) continue;` -- float promoted to double
-      st[i] = (static_cast<double>(mag) <= 1e-3) ? -1.0f : 1e10f;
-      const unsigned rank = pdr::bitrev(static_cast<unsigned>(k % R), Rbits) * Q + k / R;
-      low[i] = ((0xFFFFu - rank) << 16) | static_cast<unsigned>(k);
-    } else {
-      sx[i] = sy[i] = sz[i] = 0.0f;
-      st[i] = -1.0f;  // padding: never selectable, never updated upward
-      low[i] = 0u;
-    }
-  }
-  // this thread's points by descending `low` (= ascending tie rank): "first strictly greater wins" inside the thread
-  // is then the reference's order
-#pragma unroll
-  for (int a = 0; a < PPT - 1; ++a) {
-#pragma unroll
-    for (int c = 0; c < PPT - 1 - a; ++c) {
-      if (low[c] < low[c + 1]) {
-        float t;
-        unsigned u;
-        t = sx[c]; sx[c] = sx[c + 1]; sx[c + 1] = t;
-        t = sy[c]; sy[c] = sy[c + 1]; sy[c + 1] = t;
-        t = sz[c]; sz[c] = sz[c + 1]; sz[c + 1] = t;
-        t = st[c]; st[c] = st[c + 1]; st[c + 1] = t;
-        u = low[c]; low[c] = low[c + 1]; low[c + 1] = u;
-      }
-    }
-  }
-  fps_f2 px[PPT / 2], py[PPT / 2], pz[PPT / 2], tmp[PPT / 2];
+  FPS_LOAD_SORTED_SLOTS(T, PPT, p, N, R, Rbits, Q, tid, sx, sy, sz, st, low)
+  f2 px[PPT / 2], py[PPT / 2], pz[PPT / 2], tmp[PPT / 2];
 #pragma unroll
   for (int i = 0; i < PPT; ++i) {
     px[i >> 1][i & 1] = sx[i];
@@ -425,143 +281,35 @@ __global__ __launch_bounds__(T) void fps_lean_kernel(const float* __restrict__ x
   int old = 0;
   for (int j = 1; j < m; ++j) {
     const float4 c = lean_cloud[old];
-    constexpr int G = PPT / 2;
-    fps_f2 dx[G], dy[G], dz[G], d[G];
-#pragma unroll
-    for (int g = 0; g < G; ++g) dy[g] = py[g] - c.y;
-#pragma unroll
-    for (int g = 0; g < G; ++g) dx[g] = px[g] - c.x;
-#pragma unroll
-    for (int g = 0; g < G; ++g) d[g] = dy[g] * dy[g];          // PDR_SUM3: fma(c, c, fma(a, a, b * b))
-#pragma unroll
-    for (int g = 0; g < G; ++g) dz[g] = pz[g] - c.z;
-#pragma unroll
-    for (int g = 0; g < G; ++g) d[g] = __builtin_elementwise_fma(dx[g], dx[g], d[g]);
-#pragma unroll
-    for (int g = 0; g < G; ++g) d[g] = __builtin_elementwise_fma(dz[g], dz[g], d[g]);
     float best = -1.0f;
     unsigned bestlow = 0u;
-#pragma unroll
-    for (int g = 0; g < G; ++g) {
-      fps_f2 r;
-      asm("v_min_f32 %0, %1, %2" : "=v"(r[0]) : "v"(d[g][0]), "v"(tmp[g][0]));
-      asm("v_min_f32 %0, %1, %2" : "=v"(r[1]) : "v"(d[g][1]), "v"(tmp[g][1]));
-      tmp[g] = r;
-#pragma unroll
-      for (int e = 0; e < 2; ++e) {
+    // all pairs at once; the in-lane scan takes each pair as its minimum is ready
+    FPS_PACKED_UPDATE(PPT / 2, PPT / 2, px, py, pz, tmp, c.x, c.y, c.z,
+      _Pragma("unroll") for (int e = 0; e < 2; ++e) {
         const bool gt = r[e] > best;
         best = gt ? r[e] : best;
-        bestlow = gt ? low[2 * g + e] : bestlow;
-      }
-    }
-    // best >= 0 -> monotone uint bits; "no candidate" (-1) -> 0
-    const unsigned vb = best < 0.0f ? 0u : __float_as_uint(best);
-    const unsigned vmax = fps_wave_max_u32(vb);                 // uniform
-    // (a candidate at distance +0.0 has value bits 0 like "no candidate", but keeps its key)
-    const unsigned cand = (vb == vmax && !(best < 0.0f)) ? bestlow : 0u;
-    unsigned wlow = fps_wave_max_u32(cand);
-    unsigned long long key = pdr::u64_from(vmax, wlow);
-    if constexpr (W > 1) {
-      unsigned long long* sl = slots[j & 1];
-      if ((tid & 63) == 0) sl[tid >> 6] = key;
-      __syncthreads();
-      unsigned long long r = sl[0];
-#pragma unroll
-      for (int w = 1; w < W; ++w) {
-        const unsigned long long o = sl[w];
-        r = o > r ? o : r;
-      }
-      key = r;
-    }
+        bestlow = gt ? low[2 * pair + e] : bestlow;
+      })
+    unsigned long long key = fps::wave_argmax(best, bestlow);
+    key = fps::exchange_max<W>(slots[j & 1], key);
     old = static_cast<int>(key & 0xFFFFull);
     if (tid == 0) out[j] = old;
   }
 }
 
-template <int T, int PPT>
-int launch_lean(const float* xyz, int B, int N, int m, int R, int Rbits, int Q, int* idx, hipStream_t s) {
-  hipLaunchKernelGGL((fps_lean_kernel<T, PPT>), dim3(B), dim3(T), static_cast<size_t>(N) * sizeof(float4), s, xyz, N, m,
-                     R, Rbits, Q, idx);
-  return pdr::check_launch();
-}
-
 // Streaming fallback for N > kMaxResidentN: same ordering rule, running distances
-// in the caller's (B,N) temp (reference sampling.cpp:74-76), two-stage (value,
-// rank) arg-max.  Not on the BASELINE hot path; kept simple.
-__global__ __launch_bounds__(1024) void fps_stream_kernel(
-    const float* __restrict__ xyz, int N, int m, int R, int Rbits, int Q,
-    float* __restrict__ temp, int* __restrict__ idxs) {
-  __shared__ float sval[16];
-  __shared__ unsigned long long srank[16];
-  __shared__ int sold;
-  const int b = blockIdx.x, tid = threadIdx.x;
-  const float* p = xyz + static_cast<size_t>(b) * N * 3;
-  float* tp = temp + static_cast<size_t>(b) * N;
-  int* out = idxs + static_cast<size_t>(b) * m;
-  for (int k = tid; k < N; k += 1024) {
-    const float mag = PDR_SUM3(p[k * 3], p[k * 3 + 1], p[k * 3 + 2]);
-    tp[k] = (static_cast<double>(mag) <= 1e-3) ? -1.0f : 1e10f;
-  }
-  if (tid == 0) out[0] = 0;
-  __syncthreads();
-  int old = 0;
-  for (int j = 1; j < m; ++j) {
-    const float x1 = p[old * 3], y1 = p[old * 3 + 1], z1 = p[old * 3 + 2];
-    float best = -1.0f;
-    unsigned long long bestrank = ~0ull;  // smaller = preferred; low 32 bits = k
-    for (int k = tid; k < N; k += 1024) {
-      const float dx = p[k * 3] - x1, dy = p[k * 3 + 1] - y1, dz = p[k * 3 + 2] - z1;
-      const float d2 = fminf(PDR_SUM3(dx, dy, dz), tp[k]);
-      tp[k] = d2;
-      const unsigned long long rank =
-          (static_cast<unsigned long long>(pdr::bitrev(k % R, Rbits)) * Q + k / R) << 32 |
-          static_cast<unsigned>(k);
-      const bool better = d2 > best || (d2 == best && d2 >= 0.0f && rank < bestrank);
-      best = better ? d2 : best;
-      bestrank = better ? rank : bestrank;
-    }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-      const float ov = __shfl_xor(best, off, 64);
-      const unsigned long long orank = __shfl_xor(bestrank, off, 64);
-      const bool better = ov > best || (ov == best && orank < bestrank);
-      best = better ? ov : best;
-      bestrank = better ? orank : bestrank;
-    }
-    if ((tid & 63) == 0) {
-      sval[tid >> 6] = best;
-      srank[tid >> 6] = bestrank;
-    }
-    __syncthreads();
-    if (tid == 0) {
-      float bv = sval[0];
-      unsigned long long br = srank[0];
-      for (int w = 1; w < 16; ++w) {
-        const bool better = sval[w] > bv || (sval[w] == bv && srank[w] < br);
-        bv = better ? sval[w] : bv;
-        br = better ? srank[w] : br;
-      }
-      sold = bv < 0.0f ? 0 : static_cast<int>(br & 0xFFFFFFFFull);
-      out[j] = sold;
-    }
-    __syncthreads();
-    old = sold;
-  }
-}
+// in the caller's (B,N) temp (reference sampling.cpp:74-76); fps::stream_rounds on
+// the points as they lie in memory.  Not on the BASELINE hot path; kept simple.
+struct DenseSource {
+  const float* __restrict__ p;
+  __device__ __forceinline__ fps::Point point(int k) const { return {p[k * 3], p[k * 3 + 1], p[k * 3 + 2], 1.0f}; }
+};
 
-template <int T, int PPT>
-int launch_resident(const float* xyz, int B, int N, int m, int R, int Rbits, int Q,
-                    int* idx, hipStream_t s) {
-  const size_t lds = static_cast<size_t>((3 * N + 3) & ~3) * sizeof(float) +
-                     2 * (T / 64) * sizeof(unsigned long long);
-  // the attribute is per DEVICE: set it on every large launch (cheap host call, no global state), checked
-  if (lds > 64 * 1024 &&
-      hipFuncSetAttribute(reinterpret_cast<const void*>(&fps_resident_kernel<T, PPT>),
-                          hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-    return PDR_ELAUNCH;
-  hipLaunchKernelGGL((fps_resident_kernel<T, PPT>), dim3(B), dim3(T), lds, s, xyz, N, m, R,
-                     Rbits, Q, idx);
-  return pdr::check_launch();
+__global__ __launch_bounds__(fps::kStreamThreads) void fps_stream_kernel(const float* __restrict__ xyz, int N, int m,
+                                                          float* __restrict__ temp, int* __restrict__ idxs) {
+  const int b = blockIdx.x;
+  fps::stream_rounds(DenseSource{xyz + static_cast<size_t>(b) * N * 3}, N, m, temp + static_cast<size_t>(b) * N,
+                     idxs + static_cast<size_t>(b) * m, nullptr);
 }
 
 }  // namespace
@@ -584,14 +332,14 @@ extern "C" size_t pdr_fps_workspace_bytes(int B, int N) {
 
 namespace {
 
-// ---- the dispatch decision: ONE host function, read by the launch below and by pdr_fps_plan ------------------------
+// ---- the dispatch decision: ONE table of cells and ONE host function, read by the launch below and by pdr_fps_plan --
 enum FpsFamily { kFpsResident = 0, kFpsWave = 1, kFpsLean = 2, kFpsStream = 3 };
 
-struct FpsPlan {
-  int family, T, PPT;     // kernel family and its template parameters (stream: 1024 threads, PPT 0 = strided)
-  int R, Rbits, Q;        // the reference's thread geometry: R = opt_n_threads(N), Q = ceil(N / R); tie rank < R Q
-};
-
+// Every instantiation, once: X(family, kernel, T, PPT).  A cell carries T * PPT slots; inside a family the cells are in
+// ascending size and plan_fps takes the first one that is large enough (wave: for the R Q rank slots, lean and
+// resident: for the N points).  The launch switch is generated from the same list, so the plan cannot name a cell
+// without a launch.
+//
 // Measured on MI355X, B = 32 (tools/lab/fps_time.py), us per call:
 //                      2048->1024  1024->256  256->64  3072->1024
 //   4 waves, barrier        490        105       25        566      (fps_resident_kernel, default above 256 slots)
@@ -599,53 +347,85 @@ struct FpsPlan {
 //   4 waves, rank-ordered   532        127       20        665      (fewer VALU slots, but the round is a LATENCY
 //                                                                    chain: LDS read -> update -> tree -> 2 DPP
 //                                                                    reductions -> exchange -> index recovery)
-// so the rank-ordered variant (fps_wave_kernel) is used where it wins (<= 256 slots: no barrier at all).  Option
-// fps_wave: 0 = never, 2 = for every size up to 4096 slots (A/B and test runs).
+// so the rank-ordered variant (fps_wave_kernel) is used where it wins (<= 256 slots: no barrier at all).
+//   wave: rank-ordered slots + packed distances + tree arg-max: ONE wave while a lane holds <= 4 slots (no barrier at
+//     all), four waves (one per SIMD: a single wave issues at most one instruction every ~4-5 cycles, measured 680 ns
+//     per round with 32 slots per lane) above that;
+//   lean: the instruction-lean resident kernel, an even number of points per thread;
+//   resident: the round-1 kernel (512 / 1024 threads per cloud -- fewer points per thread against a wider exchange --,
+//     round 5, us per call at B = 32: 2048->1024 492 / 525 / 885, 1024->256 105 / 124 / 215 for 256 / 512 / 1024
+//     threads: not taken).
+#define PDR_FPS_CELLS(X)                                                                                      \
+  X(kFpsWave, fps_wave_kernel, 64, 2)        X(kFpsWave, fps_wave_kernel, 64, 4)                                \
+  X(kFpsWave, fps_wave_kernel, 256, 2)       X(kFpsWave, fps_wave_kernel, 256, 4)                               \
+  X(kFpsWave, fps_wave_kernel, 256, 8)       X(kFpsWave, fps_wave_kernel, 256, 16)                              \
+  X(kFpsLean, fps_lean_kernel, 256, 2)       X(kFpsLean, fps_lean_kernel, 256, 4)                               \
+  X(kFpsLean, fps_lean_kernel, 256, 8)       X(kFpsLean, fps_lean_kernel, 256, 12)                              \
+  X(kFpsLean, fps_lean_kernel, 256, 16)                                                                         \
+  X(kFpsResident, fps_resident_kernel, 64, 1)    X(kFpsResident, fps_resident_kernel, 64, 2)                    \
+  X(kFpsResident, fps_resident_kernel, 256, 1)   X(kFpsResident, fps_resident_kernel, 256, 2)                   \
+  X(kFpsResident, fps_resident_kernel, 256, 4)   X(kFpsResident, fps_resident_kernel, 256, 8)                   \
+  X(kFpsResident, fps_resident_kernel, 256, 12)  X(kFpsResident, fps_resident_kernel, 256, 16)                  \
+  X(kFpsResident, fps_resident_kernel, 1024, 8)  X(kFpsResident, fps_resident_kernel, 1024, 12)
+
+struct FpsCell {
+  int family, T, PPT;
+};
+#define PDR_FPS_CELL_ROW(FAMILY, KERNEL, T_, PPT_) {FAMILY, T_, PPT_},
+constexpr FpsCell kFpsCells[] = {PDR_FPS_CELLS(PDR_FPS_CELL_ROW)};
+#undef PDR_FPS_CELL_ROW
+
+struct FpsPlan {
+  int family, T, PPT;     // kernel family and its template parameters (stream: 1024 threads, PPT 0 = strided)
+  int R, Rbits, Q;        // the reference's thread geometry: R = opt_n_threads(N), Q = ceil(N / R); tie rank < R Q
+};
+
+// Option fps_wave: 0 = never, 1 = where it wins (<= 256 slots), 2 = for every size up to 4096 slots (A/B and test
+// runs).  Option fps_lean = 0: the round-1 resident kernel instead of the lean one.
 int plan_fps(int N, FpsPlan* p) {
   if (N <= 0) return PDR_EINVAL;
   p->R = pdr_opt_n_threads(N);
   p->Rbits = 0;
   while ((1 << p->Rbits) < p->R) ++p->Rbits;
   p->Q = (N + p->R - 1) / p->R;
-  const auto pick = [p](int family, int T, int PPT) {
-    p->family = family, p->T = T, p->PPT = PPT;
+  if (pdr_fps_workspace_bytes(1, N) > 0) {
+    p->family = kFpsStream, p->T = fps::kStreamThreads, p->PPT = 0;
     return PDR_OK;
-  };
-  if (pdr_fps_workspace_bytes(1, N) > 0) return pick(kFpsStream, 1024, 0);
+  }
   const long slots = static_cast<long>(p->R) * p->Q;
   const int wave_mode = pdr::option(pdr::OPT_FPS_WAVE);
   const bool use_wave = wave_mode == 2 || (wave_mode == 1 && slots <= 256);
   // the wave and lean kernels keep the cloud in N * 16 bytes of dynamic LDS next to their static exchange slots: stay
   // inside the 64 KiB a launch gets without raising hipFuncAttributeMaxDynamicSharedMemorySize, else the resident kernel
   const bool fits64k = static_cast<size_t>(N) * sizeof(float4) + 256 <= 64 * 1024;
-  if (use_wave && fits64k && slots <= 4096) {
-    // rank-ordered slots + packed distances + tree arg-max (fps_wave_kernel): ONE wave while a lane holds <= 4
-    // slots (no barrier at all), four waves (one per SIMD: a single wave issues at most one instruction every
-    // ~4-5 cycles, measured 680 ns per round with 32 slots per lane) above that
-    if (slots <= 128) return pick(kFpsWave, 64, 2);
-    if (slots <= 256) return pick(kFpsWave, 64, 4);
-    if (slots <= 512) return pick(kFpsWave, 256, 2);
-    if (slots <= 1024) return pick(kFpsWave, 256, 4);
-    if (slots <= 2048) return pick(kFpsWave, 256, 8);
-    return pick(kFpsWave, 256, 16);
-  }
-  // instruction-lean resident kernel (fps_lean_kernel): clouds whose float4 image fits the 64 KiB, an even number of
-  // points per thread.  Option fps_lean = 0: the round-1 resident kernel.
-  if (pdr::option(pdr::OPT_FPS_LEAN) != 0 && N > 128 && fits64k) {
-    if (N <= 512) return pick(kFpsLean, 256, 2);
-    if (N <= 1024) return pick(kFpsLean, 256, 4);
-    if (N <= 2048) return pick(kFpsLean, 256, 8);
-    if (N <= 3072) return pick(kFpsLean, 256, 12);
-    return pick(kFpsLean, 256, 16);
-  }
   static_assert(kMaxResidentN >= 12288, "resident path must cover the LDS-resident range");
-  // (512 / 1024 threads per cloud -- fewer points per thread against a wider exchange --, round 5, us per call at B = 32:
-  // 2048->1024 492 / 525 / 885, 1024->256 105 / 124 / 215 for 256 / 512 / 1024 threads: not taken)
-  constexpr int kResident[][2] = {{64, 1},   {64, 2},   {256, 1},   {256, 2},  {256, 4},
-                                  {256, 8},  {256, 12}, {256, 16},  {1024, 8}, {1024, 12}};
-  for (const auto& c : kResident)
-    if (N <= c[0] * c[1]) return pick(kFpsResident, c[0], c[1]);
+  int family = kFpsResident;
+  long size = N;
+  if (use_wave && fits64k && slots <= 4096) family = kFpsWave, size = slots;
+  else if (pdr::option(pdr::OPT_FPS_LEAN) != 0 && N > 128 && fits64k) family = kFpsLean;
+  for (const FpsCell& c : kFpsCells)
+    if (c.family == family && size <= static_cast<long>(c.T) * c.PPT) {
+      p->family = c.family, p->T = c.T, p->PPT = c.PPT;
+      return PDR_OK;
+    }
   return PDR_EUNSUPPORTED;
+}
+
+// One launch for the three resident families: they share the argument list and differ in the kernel and its dynamic LDS.
+using FpsKernel = void (*)(const float*, int, int, int, int, int, int*);
+int launch_fps(FpsKernel kernel, const FpsPlan& p, const float* xyz, int B, int N, int m, int* idx, hipStream_t s) {
+  // wave, lean: the cloud as float4 (static exchange slots); resident: 3 N floats and the exchange slots behind them
+  const size_t lds = p.family != kFpsResident
+                         ? static_cast<size_t>(N) * sizeof(float4)
+                         : static_cast<size_t>((3 * N + 3) & ~3) * sizeof(float) +
+                               2 * (p.T / 64) * sizeof(unsigned long long);
+  // the attribute is per DEVICE: set it on every large launch (cheap host call, no global state), checked
+  if (lds > 64 * 1024 &&
+      hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                          160 * 1024) != hipSuccess)
+    return PDR_ELAUNCH;
+  hipLaunchKernelGGL(kernel, dim3(B), dim3(p.T), lds, s, xyz, N, m, p.R, p.Rbits, p.Q, idx);
+  return pdr::check_launch();
 }
 
 }  // namespace
@@ -672,34 +452,13 @@ extern "C" int pdr_furthest_point_sampling(const float* xyz, int B, int N, int m
   if (rc != PDR_OK) return rc;
   if (p.family == kFpsStream) {
     if (!temp) return PDR_EINVAL;
-    hipLaunchKernelGGL(fps_stream_kernel, dim3(B), dim3(1024), 0, s, xyz, N, m, p.R, p.Rbits, p.Q, temp, idx);
+    hipLaunchKernelGGL(fps_stream_kernel, dim3(B), dim3(fps::kStreamThreads), 0, s, xyz, N, m, temp, idx);
     return pdr::check_launch();
   }
-  // every instantiation, keyed by what the plan reports
-#define PDR_FPS_RUN(FAMILY, LAUNCH, T_, PPT_)                  \
+#define PDR_FPS_RUN(FAMILY, KERNEL, T_, PPT_)                  \
   if (p.family == (FAMILY) && p.T == (T_) && p.PPT == (PPT_)) \
-  return LAUNCH<T_, PPT_>(xyz, B, N, m, p.R, p.Rbits, p.Q, idx, s)
-  PDR_FPS_RUN(kFpsWave, launch_wave, 64, 2);
-  PDR_FPS_RUN(kFpsWave, launch_wave, 64, 4);
-  PDR_FPS_RUN(kFpsWave, launch_wave, 256, 2);
-  PDR_FPS_RUN(kFpsWave, launch_wave, 256, 4);
-  PDR_FPS_RUN(kFpsWave, launch_wave, 256, 8);
-  PDR_FPS_RUN(kFpsWave, launch_wave, 256, 16);
-  PDR_FPS_RUN(kFpsLean, launch_lean, 256, 2);
-  PDR_FPS_RUN(kFpsLean, launch_lean, 256, 4);
-  PDR_FPS_RUN(kFpsLean, launch_lean, 256, 8);
-  PDR_FPS_RUN(kFpsLean, launch_lean, 256, 12);
-  PDR_FPS_RUN(kFpsLean, launch_lean, 256, 16);
-  PDR_FPS_RUN(kFpsResident, launch_resident, 64, 1);
-  PDR_FPS_RUN(kFpsResident, launch_resident, 64, 2);
-  PDR_FPS_RUN(kFpsResident, launch_resident, 256, 1);
-  PDR_FPS_RUN(kFpsResident, launch_resident, 256, 2);
-  PDR_FPS_RUN(kFpsResident, launch_resident, 256, 4);
-  PDR_FPS_RUN(kFpsResident, launch_resident, 256, 8);
-  PDR_FPS_RUN(kFpsResident, launch_resident, 256, 12);
-  PDR_FPS_RUN(kFpsResident, launch_resident, 256, 16);
-  PDR_FPS_RUN(kFpsResident, launch_resident, 1024, 8);
-  PDR_FPS_RUN(kFpsResident, launch_resident, 1024, 12);
+    return launch_fps(&KERNEL<T_, PPT_>, p, xyz, B, N, m, idx, s);
+  PDR_FPS_CELLS(PDR_FPS_RUN)
 #undef PDR_FPS_RUN
   return PDR_EUNSUPPORTED;
 }
