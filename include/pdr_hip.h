@@ -69,7 +69,8 @@ typedef void *pdr_stream_t; /* hipStream_t */
  *                are new; pdr_fps_ragged_workspace_bytes / pdr_fps_ragged_plan / pdr_furthest_point_sampling_ragged are
  *                new; pdr_attention_pool_cf_plan / pdr_attention_pool_cf / pdr_attention_pool_cf_grad are new;
  *                pdr_group_norm_act_workspace_bytes / pdr_group_norm_act_plan / pdr_group_norm_act /
- *                pdr_group_norm_act_grad are new. */
+ *                pdr_group_norm_act_grad are new; pdr_query_group_cf_workspace_bytes / pdr_query_group_cf_plan /
+ *                pdr_query_group_cf / pdr_query_group_cf_grad are new. */
 int pdr_version(void);
 /* last hip error string seen by this thread after a PDR_ELAUNCH ("" if none) */
 const char *pdr_last_error(void);
@@ -422,6 +423,61 @@ size_t pdr_group_norm_act_workspace_bytes(int B, int C, long S, int G);
  * aligned.  out = {family (0 scalar, 1 vector), partitions per slab P, elements per partition E, Cg}.
  * C, S or G <= 0, C < G or a NULL out: PDR_EINVAL; C S >= 2^31: PDR_EUNSUPPORTED. */
 int pdr_group_norm_act_plan(int C, long S, int G, int aligned16, long out[4]);
+/* Neighbourhood grouping of the TRAINABLE path: what QueryAndGroup.forward (pointnet2_ops/pointnet2_utils.py) does
+ * after its neighbour search, channel-first, as one differentiable op (the inference path gathers channel-last in
+ * pdr_group_build):
+ *     xyz (B,n,3), new_xyz (B,m,3), features (B,C,n) or NULL, idx (B,m,K) int32, counts (B,m) int32 or NULL
+ *     ->  out (B, Cu + 3E, m, K) f32, channels [features | relative | absolute | centre], Cu = C, or 0 when features
+ *         is NULL (C is ignored then).
+ * flags: bit 0 use_xyz (the relative channels xyz[idx] - new_xyz), bit 1 include_abs (xyz[idx]), bit 2 include_center
+ * (new_xyz, repeated over K); bits 1 and 2 are ignored without bit 0, as in the module.  E = 0 .. 3 is the number of
+ * coordinate triples the flags enable.  A non-NULL counts is the module's patch_empty: query q with counts[b,q] <= 0 is
+ * PATCHED -- absolute = the centre, relative = centre - centre, features = +0.0f, and idx is not read for it.
+ * ONE launch, no atomics, no allocation, no synchronisation: capturable.  Every output element is a bit-for-bit copy of
+ * its source or, in the relative channels, the one rounded difference a - c (no fma).  The torch composition computes a
+ * patched or passed value as 1 * a + 0 * c; this call SELECTS it: the two differ only for -0.0 and non-finite inputs.
+ * An index outside [0, n) in a slot of an unpatched query is the caller's error, as for pdr_group_points.
+ *   - two kernel families: vector (K % 4 == 0 and out 16-byte aligned: four k per thread, one 16-byte store per
+ *     channel) and scalar (anything else); the same bits.  pdr_query_group_cf_plan reports the decision.
+ *   - limits: n <= 16384, m K <= 2^22, B <= 65535, B m K < 2^31 (the inverse-index builder's, so that every forward
+ *     has its backward) and B (Cu + 3E) m K < 2^31.
+ *   - validation, decided on the host before any launch, in this order: B, m, K or C negative, n <= 0, flags outside
+ *     0 .. 7, no channel at all (without use_xyz: Cu == 0): PDR_EINVAL; B, m or K zero: PDR_OK, nothing launched, no
+ *     pointer looked at; the limits: PDR_EUNSUPPORTED; a NULL idx / out, or with use_xyz a NULL xyz / new_xyz:
+ *     PDR_EINVAL. */
+int pdr_query_group_cf(const float *xyz, const float *new_xyz, const float *features, const int *idx,
+                       const int *counts, int B, int n, int m, int K, int C, int flags, float *out,
+                       pdr_stream_t stream);
+/* Backward of pdr_query_group_cf.  idx, counts, flags: the forward's; C: the feature channels of grad_out (0 when the
+ * forward had no features); grad_out (B, C + 3E, m, K).  grad_features (B,C,n), grad_xyz (B,n,3), grad_new_xyz (B,m,3):
+ * each fully written, each may be NULL (autograd's needs_input_grad; its launches are skipped), all three NULL:
+ * PDR_EINVAL.  g_f, g_r, g_a, g_c are the slices of grad_out, a slice whose flag is off counts as +0; a slot p = (q, k)
+ * is REAL when its query is not patched and 0 <= idx[b,p] < n (an index outside is skipped, as in the *_grad_det calls):
+ *     a[d,p]               = fl(g_r[d,p] + g_a[d,p])     the absolute coordinate's gradient: xyz[idx]'s for a real slot,
+ *                                                        the centre's for a slot of a patched query
+ *     grad_features[b,c,j] = sum of g_f[b,c,p] over the real slots p with idx[b,p] == j, ascending p, fp32 from +0.0f
+ *     grad_xyz[b,j,d]      = the same sum of a[d,p]
+ *     grad_new_xyz[b,q,d]  = sum over k ascending, fp32 from +0.0f, of t_k = fl(g_c[k] - g_r[k]), and for a patched
+ *                            query t_k = fl(fl(g_c[k] - g_r[k]) + a[k]);  without use_xyz both coordinate gradients
+ *                            are +0.0f
+ * Every output element is written exactly once, there are no float atomics, the same input gives the same bits, and a
+ * cloud has the same bits alone and in a batch.  The inverse index of the *_grad_det calls (csrc/scatter_index.h) is
+ * built once per call and serves grad_features and grad_xyz; grad_new_xyz is one more kernel.  No allocation, no
+ * synchronisation: capturable.  workspace: pdr_query_group_cf_workspace_bytes(B, n, m, K) bytes, 4-byte aligned, the
+ * caller's; needed when grad_features (C > 0) or, with use_xyz, grad_xyz is asked for.  Validation: the forward's size
+ * checks in the same order (the empty problem leaves the gradient buffers alone), then the pointers. */
+int pdr_query_group_cf_grad(const int *idx, const int *counts, const float *grad_out, int B, int n, int m, int K, int C,
+                            int flags, float *grad_features, float *grad_xyz, float *grad_new_xyz, void *workspace,
+                            pdr_stream_t stream);
+/* Bytes of workspace pdr_query_group_cf_grad needs: pdr_scatter_workspace_bytes(B, m K, n) -- positive for positive
+ * sizes within the limits, 0 for an empty, invalid or unsupported problem.  Host only. */
+size_t pdr_query_group_cf_workspace_bytes(int B, int n, int m, int K);
+/* The decision pdr_query_group_cf reads.  Host only.  C: the feature channels in use (0 without features);
+ * aligned16 != 0: out is 16-byte aligned.  out = {family (0 scalar, 1 vector), grid.x (workgroups of 256 threads over
+ * the m K positions, four per thread in the vector family), grid.y (channel slabs), feature slabs (8 channels each;
+ * the coordinate channels are one more slab), output channels C + 3E, E}.  The size checks of the forward for one
+ * cloud; m or K zero or a NULL out: PDR_EINVAL. */
+int pdr_query_group_cf_plan(int n, int m, int K, int C, int flags, int aligned16, int out[6]);
 /* Voxel-grid occupancy counters of a SET of clouds (the loop of entropy_of_occupancy_grid,
  * pointnet2/models/pvd/metrics/evaluation_metrics.py:198-237, which queries a KD-tree per cloud and counts in Python):
  *     clouds (S,n,3) f32  ->  counters[c] += points of all clouds whose nearest kept grid cell is c,

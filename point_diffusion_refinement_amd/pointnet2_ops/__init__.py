@@ -5,7 +5,9 @@ knn_points: order-fixed, atomic, or (None, the default) whatever `torch.are_dete
 `set_fused_attention_pool(True | False)` (default False) makes `AttentionModule` pool with the one-launch
 `pointnet2_utils.attention_pool` and its one-launch backward instead of the torch composition.
 `set_fused_group_norm(True | False)` (default False) makes every `MyGroupNorm` of the module path, with the ReLU / Swish
-that follows it, run as the one op `pointnet2_utils.group_norm_act` instead of nn.GroupNorm, cat and activation."""
+that follows it, run as the one op `pointnet2_utils.group_norm_act` instead of nn.GroupNorm, cat and activation.
+`set_fused_grouping(True | False)` (default False) makes `QueryAndGroup` hand everything after its neighbour search to
+the one op `pointnet2_utils.query_and_group` instead of two grouping_operations, the empty-ball patch and the cats."""
 from . import pointnet2_modules, pointnet2_utils  # noqa: F401
-from ._ext import (is_deterministic, is_fused_attention_pool, is_fused_group_norm, set_deterministic,  # noqa: F401
-                   set_fused_attention_pool, set_fused_group_norm)
+from ._ext import (is_deterministic, is_fused_attention_pool, is_fused_group_norm, is_fused_grouping,  # noqa: F401
+                   set_deterministic, set_fused_attention_pool, set_fused_group_norm, set_fused_grouping)

@@ -103,6 +103,26 @@ def is_fused_group_norm():
     return _fused_group_norm
 
 
+_fused_grouping = False           # set_fused_grouping: QueryAndGroup groups with pdr_query_group_cf
+
+
+def set_fused_grouping(mode):
+    """Process-wide switch: True = `QueryAndGroup.forward` hands everything after its neighbour search to the one op
+    `pointnet2_utils.query_and_group` (one launch forward, an order-fixed backward) for fp32 GPU tensors of a size the
+    kernels support; False (the default) = the torch composition of grouping_operation, select, subtract and cat, as
+    ever.  Returns the previous setting."""
+    global _fused_grouping
+    if not isinstance(mode, bool):
+        raise TypeError("set_fused_grouping takes True or False, got %r" % (mode,))
+    prev, _fused_grouping = _fused_grouping, mode
+    return prev
+
+
+def is_fused_grouping():
+    """Whether QueryAndGroup takes the fused grouping op right now."""
+    return _fused_grouping
+
+
 def _scatter_workspace(B, P, N, device):
     """Scratch of one `*_grad_det` call (pdr_scatter_workspace_bytes), a torch allocation per call."""
     nbytes = _lib.load().pdr_scatter_workspace_bytes(int(B), int(P), int(N))
@@ -610,6 +630,113 @@ def group_norm_act_grad(x, weight, bias, mean, rstd, grad_y, num_groups, act="no
                                                        _ptr(gw), _ptr(gb), ws.data_ptr(), _stream()),
                    "group_norm_act_grad")
     return gx, gw, gb
+
+
+QUERY_GROUP_USE_XYZ, QUERY_GROUP_ABS, QUERY_GROUP_CENTER = 1, 2, 4      # the `flags` bits of pdr_query_group_cf
+
+
+def query_group_flags(use_xyz, include_abs_coordinate=False, include_center_coordinate=False):
+    """The `flags` word of query_group from the three booleans of QueryAndGroup."""
+    return ((QUERY_GROUP_USE_XYZ if use_xyz else 0) | (QUERY_GROUP_ABS if include_abs_coordinate else 0)
+            | (QUERY_GROUP_CENTER if include_center_coordinate else 0))
+
+
+def _query_group_triples(flags):
+    if not flags & QUERY_GROUP_USE_XYZ:
+        return 0
+    return 1 + bool(flags & QUERY_GROUP_ABS) + bool(flags & QUERY_GROUP_CENTER)
+
+
+def query_group_supported(B, n, m, K, C, flags):
+    """Whether pdr_query_group_cf and its backward take these sizes (C: feature channels, 0 or None without features):
+    a non-empty problem within the inverse-index builder's limits (n <= 16384, m K <= 2^22, B <= 65535) with fewer
+    than 2^31 output elements and at least one output channel."""
+    B, n, m, K, C, flags = int(B), int(n), int(m), int(K), int(C or 0), int(flags)
+    ctot = C + 3 * _query_group_triples(flags)
+    if min(B, n, m, K) <= 0 or C < 0 or not 0 <= flags <= 7 or ctot == 0:
+        return False
+    return n <= 16384 and m * K <= 2 ** 22 and B <= 65535 and B * ctot * m * K < 2 ** 31
+
+
+def _req_query_group(idx, counts, B, m):
+    _req(idx, "idx", torch.int32)
+    if idx.dim() != 3 or idx.shape[0] != B or idx.shape[1] != m:
+        raise RuntimeError("idx must have shape (B, m, K) = (%d, %d, K), got %s" % (B, m, tuple(idx.shape)))
+    if counts is not None:
+        _req(counts, "counts", torch.int32)
+        _same_device(idx, counts)
+        if tuple(counts.shape) != (B, m):
+            raise RuntimeError("counts must have shape (B, m) = (%d, %d), got %s" % (B, m, tuple(counts.shape)))
+
+
+def query_group(xyz, new_xyz, features, idx, counts, flags, out=None):
+    """The grouping head of QueryAndGroup in one launch (pdr_query_group_cf): xyz (B,n,3), new_xyz (B,m,3), features
+    (B,C,n) or None, idx (B,m,K) i32, counts (B,m) i32 or None (given: queries with counts <= 0 are patched) ->
+    (B, C + 3E, m, K) f32 with the channels [features | relative | absolute | centre] that `flags` enables.  `out`: a
+    contiguous fp32 tensor of that shape to write into (nothing is allocated then)."""
+    _req(xyz, "xyz", torch.float32)
+    _req(new_xyz, "new_xyz", torch.float32)
+    _req_xyz(xyz, "xyz")
+    _req_xyz(new_xyz, "new_xyz")
+    _same_device(xyz, new_xyz, idx)
+    B, n, _ = xyz.shape
+    m = new_xyz.shape[1]
+    if new_xyz.shape[0] != B:
+        raise RuntimeError("xyz and new_xyz must have the same batch size")
+    _req_query_group(idx, counts, B, m)
+    C = 0
+    if features is not None:
+        _req(features, "features", torch.float32)
+        _same_device(xyz, features)
+        if features.dim() != 3 or features.shape[0] != B or features.shape[2] != n:
+            raise RuntimeError("features must have shape (B, C, n) = (%d, C, %d), got %s" % (B, n, tuple(features.shape)))
+        C = int(features.shape[1])
+    K, flags = int(idx.shape[2]), int(flags)
+    shape = (B, C + 3 * _query_group_triples(flags), m, K)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=xyz.device)
+    else:
+        _req(out, "out", torch.float32)
+        _same_device(xyz, out)
+        if tuple(out.shape) != shape:
+            raise RuntimeError("out must have shape %s, got %s" % (shape, tuple(out.shape)))
+    with torch.cuda.device(xyz.device):
+        _lib.check(_lib.load().pdr_query_group_cf(xyz.data_ptr(), new_xyz.data_ptr(), _ptr(features), idx.data_ptr(),
+                                                  _ptr(counts), B, n, m, K, C, flags, out.data_ptr(), _stream()),
+                   "query_group")
+    return out
+
+
+def query_group_grad(idx, counts, grad_out, n, C, flags, need_features=True, need_xyz=True, need_new_xyz=True):
+    """Backward of query_group with a fixed summation order (pdr_query_group_cf_grad): idx, counts, flags as in the
+    forward, grad_out (B, C + 3E, m, K), n the cloud size, C the feature channels (0 without features) ->
+    (grad_features (B,C,n), grad_xyz (B,n,3), grad_new_xyz (B,m,3)), None where not needed (at least one must be;
+    grad_features is None when C == 0)."""
+    _req(grad_out, "grad_out", torch.float32)
+    if grad_out.dim() != 4:
+        raise RuntimeError("grad_out must be (B, C + 3E, m, K), got %s" % (tuple(grad_out.shape),))
+    B, ctot, m, K = (int(d) for d in grad_out.shape)
+    _req_query_group(idx, counts, B, m)
+    _same_device(grad_out, idx)
+    n, C, flags = int(n), int(C), int(flags)
+    if idx.shape[2] != K or ctot != C + 3 * _query_group_triples(flags):
+        raise RuntimeError("grad_out %s does not match idx %s, C = %d and flags = %d"
+                           % (tuple(grad_out.shape), tuple(idx.shape), C, flags))
+    dev = grad_out.device
+    gf = torch.empty((B, C, n), dtype=torch.float32, device=dev) if need_features and C > 0 else None
+    gx = torch.empty((B, n, 3), dtype=torch.float32, device=dev) if need_xyz else None
+    gn = torch.empty((B, m, 3), dtype=torch.float32, device=dev) if need_new_xyz else None
+    if B * m * K == 0:                                       # the empty problem writes nothing: every gradient is +0
+        for g in (gf, gx, gn):
+            if g is not None:
+                g.zero_()
+    nbytes = _lib.load().pdr_query_group_cf_workspace_bytes(B, n, m, K)
+    ws = torch.empty((max(int(nbytes), 4),), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().pdr_query_group_cf_grad(idx.data_ptr(), _ptr(counts), grad_out.data_ptr(), B, n, m, K, C,
+                                                       flags, _ptr(gf), _ptr(gx), _ptr(gn), ws.data_ptr(), _stream()),
+                   "query_group_grad")
+    return gf, gx, gn
 
 
 def chamfer_pairwise(x, y, x_lengths=None, y_lengths=None, symmetric=False):

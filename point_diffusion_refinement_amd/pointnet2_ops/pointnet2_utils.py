@@ -199,6 +199,47 @@ def group_norm_act(x, weight, bias, num_groups, eps=1e-5, act='none'):
     return GroupNormAct.apply(x.contiguous(), weight, bias, num_groups, eps, act)
 
 
+class QueryGroup(Function):
+    """xyz (B,n,3), new_xyz (B,m,3), features (B,C,n) | None, idx (B,m,K) i32, counts (B,m) i32 | None, flags ->
+    (B, C + 3E, m, K): _ext.query_group.  Saves idx and counts only -- every output value is a copy or one difference
+    of the inputs, so the backward needs none of them; it is order-fixed whatever set_deterministic says."""
+
+    @staticmethod
+    def forward(ctx, xyz, new_xyz, features, idx, counts, flags):
+        if counts is not None:
+            ctx.save_for_backward(idx, counts)
+        else:
+            ctx.save_for_backward(idx)
+        ctx.n, ctx.flags = xyz.shape[1], flags
+        ctx.C = 0 if features is None else features.shape[1]
+        return _ext.query_group(xyz, new_xyz, features, idx, counts, flags)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        idx = ctx.saved_tensors[0]
+        counts = ctx.saved_tensors[1] if len(ctx.saved_tensors) > 1 else None
+        need_x, need_n = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        need_f = ctx.needs_input_grad[2] and ctx.C > 0
+        if not (need_x or need_n or need_f):
+            return None, None, None, None, None, None
+        gf, gx, gn = _ext.query_group_grad(idx, counts, grad_out.contiguous().float(), ctx.n, ctx.C, ctx.flags,
+                                           need_f, need_x, need_n)
+        return gx, gn, gf, None, None, None
+
+
+def query_and_group(xyz, new_xyz, features, idx, counts=None, use_xyz=True, include_abs_coordinate=False,
+                    include_center_coordinate=False):
+    """The part of QueryAndGroup.forward after the neighbour search as one differentiable op (pdr_query_group_cf /
+    pdr_query_group_cf_grad): fp32 GPU tensors xyz (B,n,3), new_xyz (B,m,3), features (B,C,n) or None, idx (B,m,K)
+    int32, counts (B,m) int32 or None -> (B, C + 3E, m, K), channels [features | relative | absolute | centre].  A
+    `counts` tensor asks for the module's patch of empty balls: a query with counts <= 0 gets itself as every
+    neighbour and all-zero features.  Without use_xyz the two include_* flags are ignored, as in the module."""
+    flags = _ext.query_group_flags(use_xyz, include_abs_coordinate, include_center_coordinate)
+    return QueryGroup.apply(xyz.contiguous(), new_xyz.contiguous(), None if features is None else features.contiguous(),
+                            idx.contiguous(), None if counts is None else counts.contiguous(), flags)
+
+
 class BallQuery(Function):
     @staticmethod
     def forward(ctx, radius, nsample, xyz, new_xyz):
@@ -257,6 +298,11 @@ class QueryAndGroup(nn.Module):
                 return_counts=False):
         idx, counts = self._neighbours(xyz, new_xyz)
         radius_mode = self.neighbor_def == 'radius'
+        if self._takes_fused_op(xyz, new_xyz, features, idx):
+            patch_empty = (not subset) and radius_mode
+            new_features = query_and_group(xyz, new_xyz, features, idx, counts if patch_empty else None, self.use_xyz,
+                                           self.include_abs_coordinate, self.include_center_coordinate)
+            return self._finish(new_features, counts, radius_mode, record_neighbor_stats, return_counts)
         centre = new_xyz.transpose(1, 2).unsqueeze(-1)                     # (B,3,np,1)
         abs_xyz = grouping_operation(xyz.transpose(1, 2).contiguous(), idx)  # (B,3,np,K)
         patch_empty = (not subset) and radius_mode
@@ -281,7 +327,23 @@ class QueryAndGroup(nn.Module):
             if not self.use_xyz:
                 raise AssertionError("Cannot have not features and not use xyz as a feature!")
             new_features = grouped_xyz
+        return self._finish(new_features, counts, radius_mode, record_neighbor_stats, return_counts)
 
+    def _takes_fused_op(self, xyz, new_xyz, features, idx):
+        """set_fused_grouping(True), fp32 GPU tensors and a size pdr_query_group_cf takes.  (The flag is read directly
+        and before anything else: with the switch off this path calls nothing.)"""
+        if not _ext._fused_grouping:
+            return False
+        floats = [xyz, new_xyz] + ([] if features is None else [features])
+        if not all(t.is_cuda and t.dtype == torch.float32 for t in floats) or idx.dtype != torch.int32:
+            return False
+        if features is None and not self.use_xyz:
+            return False                                     # the composition raises its own error
+        flags = _ext.query_group_flags(self.use_xyz, self.include_abs_coordinate, self.include_center_coordinate)
+        C = 0 if features is None else features.shape[1]
+        return _ext.query_group_supported(xyz.shape[0], xyz.shape[1], idx.shape[1], idx.shape[2], C, flags)
+
+    def _finish(self, new_features, counts, radius_mode, record_neighbor_stats, return_counts):
         if record_neighbor_stats:
             with torch.no_grad():
                 c = counts.float()
