@@ -70,7 +70,8 @@ typedef void *pdr_stream_t; /* hipStream_t */
  *                new; pdr_attention_pool_cf_plan / pdr_attention_pool_cf / pdr_attention_pool_cf_grad are new;
  *                pdr_group_norm_act_workspace_bytes / pdr_group_norm_act_plan / pdr_group_norm_act /
  *                pdr_group_norm_act_grad are new; pdr_query_group_cf_workspace_bytes / pdr_query_group_cf_plan /
- *                pdr_query_group_cf / pdr_query_group_cf_grad are new. */
+ *                pdr_query_group_cf / pdr_query_group_cf_grad are new; pdr_knn_group_cf_workspace_bytes /
+ *                pdr_knn_group_cf_plan / pdr_knn_group_cf / pdr_knn_group_cf_grad are new. */
 int pdr_version(void);
 /* last hip error string seen by this thread after a PDR_ELAUNCH ("" if none) */
 const char *pdr_last_error(void);
@@ -478,6 +479,55 @@ size_t pdr_query_group_cf_workspace_bytes(int B, int n, int m, int K);
  * the coordinate channels are one more slab), output channels C + 3E, E}.  The size checks of the forward for one
  * cloud; m or K zero or a NULL out: PDR_EINVAL. */
 int pdr_query_group_cf_plan(int n, int m, int K, int C, int flags, int aligned16, int out[6]);
+/* Nearest-neighbour grouping of the TRAINABLE path: what group_knn(..., transpose=True)
+ * (pointnet2_ops/pointnet2_utils.py) does after its neighbour search, channel-first, as one differentiable op (the
+ * inference path gathers channel-last in pdr_knn_build):
+ *     x (B,n1,3), y (B,n2,3), features (B,C,n2) or NULL, idx (B,n1,K) int32, dists (B,n1,K) f32
+ *     ->  out (B, Cu + 11, n1, K) f32, channels [features | d2 | w | nn_abs (3) | nn_rel (3) | x (3)], Cu = C, or 0
+ *         when features is NULL (C is ignored then).
+ * idx and dists are what pdr_knn_group returned: no padding slot, 0 <= idx < n2; an index outside is the caller's
+ * error, as for pdr_query_group_cf.  ONE launch, no atomics, no allocation, no synchronisation: capturable.  The
+ * feature, d2, nn_abs and x channels are bit-for-bit copies of features[:, :, idx], dists, y[idx] and x[q];
+ * nn_rel = fl(y[idx] - x[q]); w_k = fl(r_k / S) with r_k = fl(1.0f / fl(d_k + 1e-8f)) and S the fp32 sum of r_0 ..
+ * r_{K-1} in ascending k from +0 (no fma anywhere) -- the bits of pdr_knn_group's weights.
+ *   - two kernel families: vector (K % 4 == 0 and out 16-byte aligned: four k per thread, one 16-byte store per
+ *     channel) and scalar (anything else); the same bits.  pdr_knn_group_cf_plan reports the decision.
+ *   - limits: n2 <= 16384, n1 K <= 2^22, B <= 65535, B n1 K < 2^31 (the inverse-index builder's, so that every forward
+ *     has its backward), B (Cu + 11) n1 K < 2^31 and Cu <= 524272 (the channel slabs are one grid dimension).
+ *   - validation, decided on the host before any launch, in this order: B, n1, K or C negative, n2 <= 0: PDR_EINVAL;
+ *     B, n1 or K zero: PDR_OK, nothing launched, no pointer looked at; the limits: PDR_EUNSUPPORTED; a NULL x, y, idx,
+ *     dists or out: PDR_EINVAL. */
+int pdr_knn_group_cf(const float *x, const float *y, const float *features, const int *idx, const float *dists, int B,
+                     int n1, int n2, int K, int C, float *out, pdr_stream_t stream);
+/* Backward of pdr_knn_group_cf.  x, y, idx, dists: the forward's; C: the feature channels of grad_out (0 when the
+ * forward had no features); grad_out (B, C + 11, n1, K).  grad_features (B,C,n2), grad_x (B,n1,3), grad_y (B,n2,3):
+ * each fully written, each may be NULL (autograd's needs_input_grad; its launches are skipped), all three NULL:
+ * PDR_EINVAL.  g_f, g_d, g_w, g_a, g_r, g_c are the slices of grad_out; a slot p = (q, k) is REAL when
+ * 0 <= idx[b,p] < n2 (an index outside is skipped, as in the *_grad_det calls; its e is +0).  With r_k, S, w_k as in the
+ * forward, every operation rounded to fp32, no fma:
+ *     dot = sum_k fl(g_w_k * w_k) ascending from +0;  h_k = fl(fl(g_w_k - dot) / S);
+ *     G_k = fl(g_d_k - fl(fl(r_k * r_k) * h_k));  e = fl(x[q] - y[idx]);  t = fl(fl(2 G_k) * e)
+ *     grad_x[b,q,d]        = sum over k ascending, fp32 from +0.0f, of fl(fl(g_c - g_r) + t)
+ *     grad_features[b,c,j] = sum of g_f[b,c,p] over the real slots p with idx[b,p] == j, ascending p, fp32 from +0.0f
+ *     grad_y[b,j,d]        = the same ordered sum of fl(fl(g_a + g_r) - t)
+ * Every output element is written exactly once, there are no float atomics, the same input gives the same bits, and a
+ * cloud has the same bits alone and in a batch.  The inverse index of the *_grad_det calls (csrc/scatter_index.h) is
+ * built once per call and serves grad_features and grad_y; grad_x is one more kernel and needs no index.  No
+ * allocation, no synchronisation: capturable.  workspace: pdr_knn_group_cf_workspace_bytes(B, n1, n2, K) bytes, 4-byte
+ * aligned, the caller's; needed when grad_features (C > 0) or grad_y is asked for.  Validation: the forward's size
+ * checks in the same order (the empty problem leaves the gradient buffers alone), then the pointers. */
+int pdr_knn_group_cf_grad(const float *x, const float *y, const int *idx, const float *dists, const float *grad_out,
+                          int B, int n1, int n2, int K, int C, float *grad_features, float *grad_x, float *grad_y,
+                          void *workspace, pdr_stream_t stream);
+/* Bytes of workspace pdr_knn_group_cf_grad needs: pdr_scatter_workspace_bytes(B, n1 K, n2) -- positive for positive
+ * sizes within the limits, 0 for an empty, invalid or unsupported problem.  Host only. */
+size_t pdr_knn_group_cf_workspace_bytes(int B, int n1, int n2, int K);
+/* The decision pdr_knn_group_cf reads.  Host only.  C: the feature channels in use (0 without features);
+ * aligned16 != 0: out is 16-byte aligned.  out = {family (0 scalar, 1 vector), grid.x (workgroups of 256 threads over
+ * the n1 K positions, four per thread in the vector family), grid.y (channel slabs), feature slabs (8 channels each;
+ * the 11 geometric channels are one more slab), output channels C + 11}.  The size checks of the forward for one
+ * cloud; n1 or K zero or a NULL out: PDR_EINVAL. */
+int pdr_knn_group_cf_plan(int n1, int n2, int K, int C, int aligned16, int out[5]);
 /* Voxel-grid occupancy counters of a SET of clouds (the loop of entropy_of_occupancy_grid,
  * pointnet2/models/pvd/metrics/evaluation_metrics.py:198-237, which queries a KD-tree per cloud and counts in Python):
  *     clouds (S,n,3) f32  ->  counters[c] += points of all clouds whose nearest kept grid cell is c,

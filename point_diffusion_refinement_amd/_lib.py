@@ -58,6 +58,10 @@ SIGNATURES = {
     "pdr_query_group_cf_plan": (_I, [_I, _I, _I, _I, _I, _I, _P]),
     "pdr_query_group_cf": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P]),
     "pdr_query_group_cf_grad": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "pdr_knn_group_cf_workspace_bytes": (_Z, [_I, _I, _I, _I]),
+    "pdr_knn_group_cf_plan": (_I, [_I, _I, _I, _I, _I, _P]),
+    "pdr_knn_group_cf": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P]),
+    "pdr_knn_group_cf_grad": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "pdr_occupancy_grid": (_I, [_P, _P, _I, _I, _I, _P, _P, _I, _P, _P, _P, _P]),
     "pdr_knn_group": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
     "pdr_knn_plan": (_I, [_I, _I, _I, _I, _I, _I, _P]),

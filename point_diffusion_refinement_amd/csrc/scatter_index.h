@@ -1,6 +1,7 @@
 // scatter_index.h -- the inverse index that turns a scatter-add into an order-fixed gather, and the two ordered sums
-// over it.  Shared by scatter_det.hip (the four *_grad_det calls) and query_group_cf.hip (pdr_query_group_cf_grad);
-// everything here has internal linkage, each file gets its own copy of the kernels.
+// over it.  Shared by scatter_det.hip (the four *_grad_det calls), query_group_cf.hip (pdr_query_group_cf_grad) and
+// knn_group_cf.hip (pdr_knn_group_cf_grad); everything here has internal linkage, each file gets its own copy of the
+// kernels.
 //
 // An INVERSE INDEX lists, for every destination, its source positions in ascending order, and one thread (or, for a
 // very long list, one lane of a wave) adds them in exactly that order in fp32 from +0.0f -- the order of the CPU

@@ -7,7 +7,11 @@ knn_points: order-fixed, atomic, or (None, the default) whatever `torch.are_dete
 `set_fused_group_norm(True | False)` (default False) makes every `MyGroupNorm` of the module path, with the ReLU / Swish
 that follows it, run as the one op `pointnet2_utils.group_norm_act` instead of nn.GroupNorm, cat and activation.
 `set_fused_grouping(True | False)` (default False) makes `QueryAndGroup` hand everything after its neighbour search to
-the one op `pointnet2_utils.query_and_group` instead of two grouping_operations, the empty-ball patch and the cats."""
+the one op `pointnet2_utils.query_and_group` instead of two grouping_operations, the empty-ball patch and the cats.
+`set_fused_knn_grouping(True | False)` (default False) makes `group_knn(..., transpose=True)` hand everything after its
+neighbour search to the one op `pointnet2_utils.knn_and_group` instead of knn_gather, the weight arithmetic, the cat
+and two transposes."""
 from . import pointnet2_modules, pointnet2_utils  # noqa: F401
 from ._ext import (is_deterministic, is_fused_attention_pool, is_fused_group_norm, is_fused_grouping,  # noqa: F401
-                   set_deterministic, set_fused_attention_pool, set_fused_group_norm, set_fused_grouping)
+                   is_fused_knn_grouping, set_deterministic, set_fused_attention_pool, set_fused_group_norm,
+                   set_fused_grouping, set_fused_knn_grouping)

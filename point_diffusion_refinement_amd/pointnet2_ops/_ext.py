@@ -123,6 +123,26 @@ def is_fused_grouping():
     return _fused_grouping
 
 
+_fused_knn_grouping = False       # set_fused_knn_grouping: group_knn groups with pdr_knn_group_cf
+
+
+def set_fused_knn_grouping(mode):
+    """Process-wide switch: True = `group_knn(..., transpose=True)` searches with `knn_group` and hands everything after
+    the search to the one op `pointnet2_utils.knn_and_group` (one launch forward, an order-fixed backward) for fp32 GPU
+    tensors with K <= min(n2, 16) and a size the kernels support; False (the default) = the torch composition of
+    knn_points, knn_gather, the weight arithmetic, cat and two transposes, as ever.  Returns the previous setting."""
+    global _fused_knn_grouping
+    if not isinstance(mode, bool):
+        raise TypeError("set_fused_knn_grouping takes True or False, got %r" % (mode,))
+    prev, _fused_knn_grouping = _fused_knn_grouping, mode
+    return prev
+
+
+def is_fused_knn_grouping():
+    """Whether group_knn takes the fused grouping op right now."""
+    return _fused_knn_grouping
+
+
 def _scatter_workspace(B, P, N, device):
     """Scratch of one `*_grad_det` call (pdr_scatter_workspace_bytes), a torch allocation per call."""
     nbytes = _lib.load().pdr_scatter_workspace_bytes(int(B), int(P), int(N))
@@ -737,6 +757,97 @@ def query_group_grad(idx, counts, grad_out, n, C, flags, need_features=True, nee
                                                        flags, _ptr(gf), _ptr(gx), _ptr(gn), ws.data_ptr(), _stream()),
                    "query_group_grad")
     return gf, gx, gn
+
+
+KNN_GROUP_GEO = 11                # d2 | w | nn_abs (3) | nn_rel (3) | x (3): the channels group_knn adds to the features
+
+
+def knn_group_cf_supported(B, n1, n2, K, C):
+    """Whether pdr_knn_group_cf and its backward take these sizes (C: feature channels, 0 or None without features):
+    a non-empty problem within the inverse-index builder's limits (n2 <= 16384, n1 K <= 2^22, B <= 65535) with fewer
+    than 2^31 output elements and at most 524272 feature channels (the slabs of 8 are one grid dimension)."""
+    B, n1, n2, K, C = int(B), int(n1), int(n2), int(K), int(C or 0)
+    if min(B, n1, n2, K) <= 0 or C < 0:
+        return False
+    return (n2 <= 16384 and n1 * K <= 2 ** 22 and B <= 65535 and B * (C + KNN_GROUP_GEO) * n1 * K < 2 ** 31
+            and C <= 8 * 65534)
+
+
+def _req_knn_group_cf(x, y, idx, dists):
+    _req(x, "x", torch.float32)
+    _req(y, "y", torch.float32)
+    _req_xyz(x, "x")
+    _req_xyz(y, "y")
+    _req(idx, "idx", torch.int32)
+    _req(dists, "dists", torch.float32)
+    _same_device(x, y, idx, dists)
+    B, n1, _ = x.shape
+    if y.shape[0] != B:
+        raise RuntimeError("x and y must have the same batch size")
+    if idx.dim() != 3 or idx.shape[0] != B or idx.shape[1] != n1:
+        raise RuntimeError("idx must have shape (B, n1, K) = (%d, %d, K), got %s" % (B, n1, tuple(idx.shape)))
+    if dists.shape != idx.shape:
+        raise RuntimeError("dists must have idx's shape %s, got %s" % (tuple(idx.shape), tuple(dists.shape)))
+    return int(B), int(n1), int(y.shape[1]), int(idx.shape[2])
+
+
+def knn_group_cf(x, y, features, idx, dists, out=None):
+    """The grouping head of group_knn(..., transpose=True) in one launch (pdr_knn_group_cf): x (B,n1,3), y (B,n2,3),
+    features (B,C,n2) or None, idx (B,n1,K) i32 and dists (B,n1,K) f32 as `knn_group` returns them ->
+    (B, C + 11, n1, K) f32 with the channels [features | d2 | w | nn_abs | nn_rel | x].  `out`: a contiguous fp32 tensor
+    of that shape to write into (nothing is allocated then)."""
+    B, n1, n2, K = _req_knn_group_cf(x, y, idx, dists)
+    C = 0
+    if features is not None:
+        _req(features, "features", torch.float32)
+        _same_device(x, features)
+        if features.dim() != 3 or features.shape[0] != B or features.shape[2] != n2:
+            raise RuntimeError("features must have shape (B, C, n2) = (%d, C, %d), got %s" % (B, n2, tuple(features.shape)))
+        C = int(features.shape[1])
+    shape = (B, C + KNN_GROUP_GEO, n1, K)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=x.device)
+    else:
+        _req(out, "out", torch.float32)
+        _same_device(x, out)
+        if tuple(out.shape) != shape:
+            raise RuntimeError("out must have shape %s, got %s" % (shape, tuple(out.shape)))
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.load().pdr_knn_group_cf(x.data_ptr(), y.data_ptr(), _ptr(features), idx.data_ptr(),
+                                                dists.data_ptr(), B, n1, n2, K, C, out.data_ptr(), _stream()),
+                   "knn_group_cf")
+    return out
+
+
+def knn_group_cf_grad(x, y, idx, dists, grad_out, C, need_features=True, need_x=True, need_y=True):
+    """Backward of knn_group_cf with a fixed summation order (pdr_knn_group_cf_grad): x, y, idx, dists as in the
+    forward, grad_out (B, C + 11, n1, K), C the feature channels (0 without features) ->
+    (grad_features (B,C,n2), grad_x (B,n1,3), grad_y (B,n2,3)), None where not needed (at least one must be;
+    grad_features is None when C == 0)."""
+    B, n1, n2, K = _req_knn_group_cf(x, y, idx, dists)
+    _req(grad_out, "grad_out", torch.float32)
+    _same_device(x, grad_out)
+    C = int(C)
+    if tuple(grad_out.shape) != (B, C + KNN_GROUP_GEO, n1, K):
+        raise RuntimeError("grad_out must be (B, C + 11, n1, K) = %s, got %s"
+                           % ((B, C + KNN_GROUP_GEO, n1, K), tuple(grad_out.shape)))
+    dev = x.device
+    gf = torch.empty((B, C, n2), dtype=torch.float32, device=dev) if need_features and C > 0 else None
+    gx = torch.empty((B, n1, 3), dtype=torch.float32, device=dev) if need_x else None
+    gy = torch.empty((B, n2, 3), dtype=torch.float32, device=dev) if need_y else None
+    if B * n1 * K == 0:                                      # the empty problem writes nothing: every gradient is +0
+        for g in (gf, gx, gy):
+            if g is not None:
+                g.zero_()
+    ws = None                                                # the inverse index: grad_x alone builds none
+    if gf is not None or gy is not None:
+        nbytes = _lib.load().pdr_knn_group_cf_workspace_bytes(B, n1, n2, K)
+        ws = torch.empty((max(int(nbytes), 4),), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().pdr_knn_group_cf_grad(x.data_ptr(), y.data_ptr(), idx.data_ptr(), dists.data_ptr(),
+                                                     grad_out.data_ptr(), B, n1, n2, K, C, _ptr(gf), _ptr(gx), _ptr(gy),
+                                                     _ptr(ws), _stream()), "knn_group_cf_grad")
+    return gf, gx, gy
 
 
 def chamfer_pairwise(x, y, x_lengths=None, y_lengths=None, symmetric=False):

@@ -7,6 +7,9 @@ the reference's pointnet2_ops/pointnet2_utils.py, running on libpdr_hip.so.
     count_to_mask, average_feature           (:36,46)
     attention_pool                           (attention.py:71-77 as one op: masked softmax over K and the weighted
                                               sum of the values, with a one-launch backward that saves no weights)
+    query_and_group, knn_and_group           (what QueryAndGroup / group_knn do after their neighbour search, each as
+                                              one op with an order-fixed backward; behind set_fused_grouping /
+                                              set_fused_knn_grouping, default off)
 
 kNN comes from this package's own `_ext.knn_points` (the reference imports
 pytorch3d.ops.knn, :7).  Autograd: FPS / ball_query / three_nn are
@@ -370,6 +373,56 @@ class GroupAll(nn.Module):
         return torch.cat([gfeat, gxyz], dim=1) if self.use_xyz else gfeat
 
 
+class KnnGroup(Function):
+    """x (B,n1,3), y (B,n2,3), features (B,C,n2) | None, idx (B,n1,K) i32, dists (B,n1,K) f32 -> (B, C + 11, n1, K):
+    _ext.knn_group_cf.  Saves x, y, idx and dists only -- no float tensor of output size; the backward recomputes the
+    weights from dists and is order-fixed whatever set_deterministic says."""
+
+    @staticmethod
+    def forward(ctx, x, y, features, idx, dists):
+        ctx.save_for_backward(x, y, idx, dists)
+        ctx.C = 0 if features is None else features.shape[1]
+        return _ext.knn_group_cf(x, y, features, idx, dists)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        x, y, idx, dists = ctx.saved_tensors
+        need_x, need_y = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        need_f = ctx.needs_input_grad[2] and ctx.C > 0
+        if not (need_x or need_y or need_f):
+            return None, None, None, None, None
+        gf, gx, gy = _ext.knn_group_cf_grad(x, y, idx, dists, grad_out.contiguous().float(), ctx.C, need_f, need_x, need_y)
+        return gx, gy, gf, None, None
+
+
+def knn_and_group(x, y, features, idx, dists):
+    """The part of group_knn(..., transpose=True) after the neighbour search as one differentiable op
+    (pdr_knn_group_cf / pdr_knn_group_cf_grad): fp32 GPU tensors x (B,n1,3), y (B,n2,3), features (B,C,n2) or None,
+    idx (B,n1,K) int32 and dists (B,n1,K) as `_ext.knn_group` returns them (no padding slot) -> (B, C + 11, n1, K)
+    contiguous, channels [features | d2 | w | nn_abs | nn_rel | x].  `dists` is taken as the squared distance
+    |x - y[idx]|^2 that the search computed: its gradient flows to x and y inside the op, not to `dists`."""
+    return KnnGroup.apply(x.contiguous(), y.contiguous(), None if features is None else features.contiguous(),
+                          idx.contiguous(), dists.detach().contiguous())
+
+
+def _group_knn_takes_fused_op(x, y, features_at_y, K, transpose):
+    """set_fused_knn_grouping(True), transpose=True, fp32 GPU tensors, K <= min(n2, 16) (pdr_knn_group's contract: no
+    padding slot) and a size pdr_knn_group_cf takes.  (The flag is read directly and before anything else: with the
+    switch off this path calls nothing.)"""
+    if not _ext._fused_knn_grouping:
+        return False
+    if not transpose or not all(torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32
+                                for t in (x, y, features_at_y)):
+        return False
+    if x.dim() != 3 or y.dim() != 3 or features_at_y.dim() != 3 or features_at_y.shape[2] != y.shape[1]:
+        return False                                         # the composition raises its own error
+    K = int(K)
+    if K > min(y.shape[1], 16):
+        return False
+    return _ext.knn_group_cf_supported(x.shape[0], x.shape[1], y.shape[1], K, features_at_y.shape[1])
+
+
 def group_knn(x, y, features_at_y, K, transpose=False):
     """K nearest neighbours of x (B,N1,3) in y (B,N2,3) with 11 geometric channels.
 
@@ -377,6 +430,9 @@ def group_knn(x, y, features_at_y, K, transpose=False):
     or its (B,C+11,N1,K) view when transpose=True (features_at_y then is (B,C,N2)).
     The inverse-distance weights use the SQUARED distances (reference :500-503).
     """
+    if _group_knn_takes_fused_op(x, y, features_at_y, K, transpose):
+        d2, idx, _ = _ext.knn_group(x.detach().contiguous(), y.detach().contiguous(), K)
+        return knn_and_group(x, y, features_at_y, idx, d2)
     feats_y = features_at_y.transpose(1, 2).contiguous() if transpose else features_at_y
     d2, idx, nn_abs = _ext.knn_points(x, y, K, return_nn=True)
     # K > N2: knn_points pads missing neighbours with idx -1 (dist 0, nn 0).  pytorch3d zero-initialises idx, so
