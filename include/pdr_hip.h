@@ -71,7 +71,9 @@ typedef void *pdr_stream_t; /* hipStream_t */
  *                pdr_group_norm_act_workspace_bytes / pdr_group_norm_act_plan / pdr_group_norm_act /
  *                pdr_group_norm_act_grad are new; pdr_query_group_cf_workspace_bytes / pdr_query_group_cf_plan /
  *                pdr_query_group_cf / pdr_query_group_cf_grad are new; pdr_knn_group_cf_workspace_bytes /
- *                pdr_knn_group_cf_plan / pdr_knn_group_cf / pdr_knn_group_cf_grad are new. */
+ *                pdr_knn_group_cf_plan / pdr_knn_group_cf / pdr_knn_group_cf_grad are new;
+ *                pdr_relu_group_norm_cf_workspace_bytes / pdr_relu_group_norm_cf_plan / pdr_relu_group_norm_cf /
+ *                pdr_relu_group_norm_cf_grad are new. */
 int pdr_version(void);
 /* last hip error string seen by this thread after a PDR_ELAUNCH ("" if none) */
 const char *pdr_last_error(void);
@@ -424,6 +426,61 @@ size_t pdr_group_norm_act_workspace_bytes(int B, int C, long S, int G);
  * aligned.  out = {family (0 scalar, 1 vector), partitions per slab P, elements per partition E, Cg}.
  * C, S or G <= 0, C < G or a NULL out: PDR_EINVAL; C S >= 2^31: PDR_EUNSUPPORTED. */
 int pdr_group_norm_act_plan(int C, long S, int G, int aligned16, long out[4]);
+/* The front of AttentionModule's score head on the TRAINABLE path (pointnet2_ops/attention.py: expand, cat, then
+ * weight_conv's ReLU and MyGroupNorm -- activation FIRST, then norm) as one differentiable op over a tensor that is
+ * never built:
+ *     k (B,C2,N,K) f32 dense, C2 >= 1;  q (B,C1,N) f32 dense, or NULL with C1 = 0;  gamma, beta (Cn) f32, both NULL = 1, 0
+ *     ->  y (B,C,N,K) f32 contiguous, C = C1 + C2;  mean, rstd (B,G) f32 (either may be NULL).
+ * The virtual input is x = cat([q[..., None] repeated K times, k], dim 1), S = N K.  u = relu(x) on ALL channels
+ * (x > 0 ? x : +0; a NaN stays a NaN, as torch.relu leaves it); Cn = C - C % G, Cg = Cn / G; group g of cloud b is the
+ * virtual channels [g Cg, (g + 1) Cg) -- inside q, inside k, or across the boundary --, m = Cg S values:
+ *     mean, biased variance, rstd = 1 / sqrt(var + eps);  c < Cn: y = (u - mean) rstd gamma[c] + beta[c];  c >= Cn: y = u.
+ * TWO launches (statistics partials, then apply), no atomics, no allocation, no synchronisation: capturable.  Every
+ * output element is written exactly once; the same input gives the same bits, and cloud b of a batched call has the
+ * bits of the B = 1 call on that cloud.
+ *   - operation chain (csrc/relu_group_norm.hip states it in full): moments in double; a q value is read once and the
+ *     double sums over the slab's q values are multiplied by double(K) (one rounding each); mean_d = S1 / m,
+ *     var_d = max(S2 / m - mean_d^2, 0); mean = float(mean_d), rstd = float(1 / sqrt(var_d + eps)) are the values
+ *     written AND applied; then, one fp32 rounding each, d = u - mean, xh = d rstd, y = fma(xh, gamma, beta).
+ *   - summation order: a function of (C1, Cg, N, K) and the kernel family only.  The k values of a slab are cut into
+ *     P <= 32 partitions of E elements (E a multiple of 1024, at least 8192, from m = Cg S alone;
+ *     pdr_relu_group_norm_cf_plan reports both), the slab's q values are one more partition (V = 1); inside a partition
+ *     thread t of 256 takes elements (256 i + t) V .. + V - 1, i ascending, then a lane butterfly, the four waves
+ *     ascending; the q term first, then the P partials ascending.
+ *   - two kernel families: vector (V = 4: K % 4 == 0 and k, y 16-byte aligned) and scalar (V = 1: anything else).
+ *   - workspace: pdr_relu_group_norm_cf_workspace_bytes(B, C1, C2, N, K, G) bytes, 8-byte aligned, the caller's; it
+ *     serves either call (forward: B G (P + 1) pairs of doubles; backward: B C pairs).
+ *   - validation, on the host before any launch, in this order: B, C1, N or K negative, C2 < 1, G < 1, eps negative or
+ *     NaN: PDR_EINVAL; C1 + C2 < G: PDR_EINVAL; B N K == 0: PDR_OK, nothing launched, no pointer looked at;
+ *     B C N K >= 2^31 or B C >= 2^24 (a grid's x dimension; every y dimension is at most 65535 by construction):
+ *     PDR_EUNSUPPORTED; a NULL k / y / workspace, C1 > 0 with a NULL q, or exactly one of gamma / beta NULL: PDR_EINVAL. */
+int pdr_relu_group_norm_cf(const float *q, const float *k, const float *gamma, const float *beta, int B, int C1,
+                           int C2, int N, int K, int G, float eps, float *y, float *mean, float *rstd,
+                           void *workspace, pdr_stream_t stream);
+/* Backward of pdr_relu_group_norm_cf.  mean, rstd: what the forward wrote; grad_y (B,C,N,K); grad_q (B,C1,N), grad_k
+ * (B,C2,N,K), grad_gamma, grad_beta (Cn), each fully written, each may be NULL (not wanted); all four NULL, gamma NULL
+ * with a non-NULL grad_gamma / grad_beta, or grad_q with C1 == 0: PDR_EINVAL.  The kernels recompute u, d, xh from q, k
+ * and the saved statistics by the forward's sequence (the forward's bits), then
+ *     r1[b,c] = sum_s grad_y xh,  r2[b,c] = sum_s grad_y       in double, to the workspace, order as a partition's
+ *     c1 = sum_c gamma r1,  c2 = sum_c gamma r2                over the slab's Cg rows, ascending, in double
+ *     du = rstd (gamma grad_y - fma(xh, float(c1 / m), float(c2 / m)));   pass-through channel: du = grad_y
+ *     dx = x > 0 ? du : +0   (the mask is on the raw input);   grad_k = dx on the k channels
+ *     grad_q[b,c,n] = x > 0 ? float(sum_j double(du[b,c,n,j])) : +0    a double sum over j = 0 .. K - 1, ascending from
+ *                     +0, rounded once; the q part of dx is never stored
+ *     dgamma[c] = sum_b r1[b,c],  dbeta[c] = sum_b r2[b,c]     ascending b, in double, rounded once
+ * Up to FOUR launches (row sums, grad_k, grad_q, parameter sums; those not asked for are skipped), no atomics, no
+ * allocation, no synchronisation: capturable; the same input gives the same bits.  Kernel families as the forward (k,
+ * grad_y and grad_k aligned).  Validation: the forward's size checks in the same order, then the pointers. */
+int pdr_relu_group_norm_cf_grad(const float *q, const float *k, const float *gamma, const float *beta,
+                                const float *mean, const float *rstd, const float *grad_y, int B, int C1, int C2, int N,
+                                int K, int G, float *grad_q, float *grad_k, float *grad_gamma, float *grad_beta,
+                                void *workspace, pdr_stream_t stream);
+/* Bytes of workspace either call above needs; 0 for an empty, invalid or unsupported problem.  Host only. */
+size_t pdr_relu_group_norm_cf_workspace_bytes(int B, int C1, int C2, int N, int K, int G);
+/* The decision the two calls above read.  Host only.  aligned16 != 0: the tensor pointers of the call are 16-byte
+ * aligned.  out = {family (0 scalar, 1 vector), k partitions per slab P, elements per partition E, Cg}.
+ * C1 < 0, C2, N, K or G < 1, C1 + C2 < G or a NULL out: PDR_EINVAL; C N K >= 2^31 or C >= 2^24: PDR_EUNSUPPORTED. */
+int pdr_relu_group_norm_cf_plan(int C1, int C2, int N, int K, int G, int aligned16, long out[4]);
 /* Neighbourhood grouping of the TRAINABLE path: what QueryAndGroup.forward (pointnet2_ops/pointnet2_utils.py) does
  * after its neighbour search, channel-first, as one differentiable op (the inference path gathers channel-last in
  * pdr_group_build):

@@ -10,8 +10,11 @@ that follows it, run as the one op `pointnet2_utils.group_norm_act` instead of n
 the one op `pointnet2_utils.query_and_group` instead of two grouping_operations, the empty-ball patch and the cats.
 `set_fused_knn_grouping(True | False)` (default False) makes `group_knn(..., transpose=True)` hand everything after its
 neighbour search to the one op `pointnet2_utils.knn_and_group` instead of knn_gather, the weight arithmetic, the cat
-and two transposes."""
+and two transposes.
+`set_fused_score_norm(True | False)` (default False) makes `AttentionModule` run the front of its score head -- expand,
+cat, then each [ReLU, MyGroupNorm] pair of `weight_conv` -- as the one op `pointnet2_utils.relu_group_norm`, which
+never builds the cat."""
 from . import pointnet2_modules, pointnet2_utils  # noqa: F401
 from ._ext import (is_deterministic, is_fused_attention_pool, is_fused_group_norm, is_fused_grouping,  # noqa: F401
-                   is_fused_knn_grouping, set_deterministic, set_fused_attention_pool, set_fused_group_norm,
-                   set_fused_grouping, set_fused_knn_grouping)
+                   is_fused_knn_grouping, is_fused_score_norm, set_deterministic, set_fused_attention_pool,
+                   set_fused_group_norm, set_fused_grouping, set_fused_knn_grouping, set_fused_score_norm)

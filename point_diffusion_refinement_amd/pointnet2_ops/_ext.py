@@ -143,6 +143,26 @@ def is_fused_knn_grouping():
     return _fused_knn_grouping
 
 
+_fused_score_norm = False         # set_fused_score_norm: AttentionModule's score head runs pdr_relu_group_norm_cf
+
+
+def set_fused_score_norm(mode):
+    """Process-wide switch: True = `AttentionModule.forward` skips the expand and the cat of its score head and runs each
+    [ReLU, MyGroupNorm] pair of `weight_conv` as one `relu_group_norm` op (and its backward) for fp32 GPU tensors of a
+    shape the kernels support; False (the default) = the torch composition, as ever.  Independent of the other
+    switches.  Returns the previous setting."""
+    global _fused_score_norm
+    if not isinstance(mode, bool):
+        raise TypeError("set_fused_score_norm takes True or False, got %r" % (mode,))
+    prev, _fused_score_norm = _fused_score_norm, mode
+    return prev
+
+
+def is_fused_score_norm():
+    """Whether AttentionModule's score head takes the fused ReLU + GroupNorm op right now."""
+    return _fused_score_norm
+
+
 def _scatter_workspace(B, P, N, device):
     """Scratch of one `*_grad_det` call (pdr_scatter_workspace_bytes), a torch allocation per call."""
     nbytes = _lib.load().pdr_scatter_workspace_bytes(int(B), int(P), int(N))
@@ -652,7 +672,92 @@ def group_norm_act_grad(x, weight, bias, mean, rstd, grad_y, num_groups, act="no
     return gx, gw, gb
 
 
-QUERY_GROUP_USE_XYZ, QUERY_GROUP_ABS, QUERY_GROUP_CENTER = 1, 2, 4      # the `flags` bits of pdr_query_group_cf
+def _req_relu_group_norm(q, k, weight, bias, num_groups):
+    """Shapes and dtypes of relu_group_norm's inputs; returns (B, C1, C2, N, K, G)."""
+    _req(k, "k", torch.float32)
+    if k.dim() != 4:
+        raise RuntimeError("relu_group_norm: k must be (B, C2, N, K), got %s" % (tuple(k.shape),))
+    B, C2, N, K = (int(d) for d in k.shape)
+    C1, G = 0, int(num_groups)
+    if q is not None:
+        _req(q, "q", torch.float32)
+        _same_device(k, q)
+        if q.dim() != 3 or int(q.shape[0]) != B or int(q.shape[2]) != N:
+            raise RuntimeError("q must have shape (B, C1, N) = (%d, C1, %d), got %s" % (B, N, tuple(q.shape)))
+        C1 = int(q.shape[1])
+    if (weight is None) != (bias is None):
+        raise RuntimeError("relu_group_norm: weight and bias must both be given or both be None")
+    if weight is not None:
+        C = C1 + C2
+        cn = C - C % G if G > 0 else -1
+        for t, name in ((weight, "weight"), (bias, "bias")):
+            _req(t, name, torch.float32)
+            _same_device(k, t)
+            if tuple(t.shape) != (cn,):
+                raise RuntimeError("%s must have shape (C - C %% G,) = (%d,), got %s" % (name, cn, tuple(t.shape)))
+    return B, C1, C2, N, K, G
+
+
+def _relu_group_norm_workspace(B, C1, C2, N, K, G, device):
+    nbytes = _lib.load().pdr_relu_group_norm_cf_workspace_bytes(B, C1, C2, N, K, G)
+    return torch.empty(max(nbytes // 8, 1), dtype=torch.float64, device=device)
+
+
+def relu_group_norm_supported(C1, k_shape, num_groups):
+    """Whether pdr_relu_group_norm_cf takes q (B, C1, N) (C1 = 0: no q) with k of shape (B, C2, N, K): at least one k
+    channel, at least `num_groups` channels in all, fewer than 2^31 output elements and fewer than 2^24 (b, c) rows."""
+    if len(k_shape) != 4:
+        return False
+    B, C2, N, K = (int(d) for d in k_shape)
+    C = int(C1) + C2
+    return int(C1) >= 0 and C2 >= 1 and 0 < int(num_groups) <= C and B * C < 2 ** 24 and B * C * N * K < 2 ** 31
+
+
+def relu_group_norm(q, k, weight, bias, num_groups, eps=1e-5):
+    """MyGroupNorm(relu(cat([q broadcast over K, k], 1))) in two launches (pdr_relu_group_norm_cf) without the cat:
+    q (B, C1, N) f32 or None, k (B, C2, N, K) f32, weight / bias (C - C % G) f32 or both None, C = C1 + C2
+    -> (y (B, C, N, K), mean (B, G), rstd (B, G)).  Channels past C - C % G are not normalised (ReLU only)."""
+    B, C1, C2, N, K, G = _req_relu_group_norm(q, k, weight, bias, num_groups)
+    y = torch.empty((B, C1 + C2, N, K), dtype=torch.float32, device=k.device)
+    mean = torch.empty((B, max(G, 0)), dtype=torch.float32, device=k.device)
+    rstd = torch.empty_like(mean)
+    ws = _relu_group_norm_workspace(B, C1, C2, N, K, G, k.device)
+    with torch.cuda.device(k.device):
+        _lib.check(_lib.load().pdr_relu_group_norm_cf(_ptr(q), k.data_ptr(), _ptr(weight), _ptr(bias), B, C1, C2, N, K,
+                                                      G, float(eps), y.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
+                                                      ws.data_ptr(), _stream()), "relu_group_norm")
+    return y, mean, rstd
+
+
+def relu_group_norm_grad(q, k, weight, bias, mean, rstd, grad_y, num_groups, need_q=True, need_k=True,
+                         need_weight=True, need_bias=True):
+    """Backward of relu_group_norm in up to four launches (pdr_relu_group_norm_cf_grad): recomputes the normalised
+    values from q, k and the saved (B, G) statistics.  -> (grad_q, grad_k, grad_weight, grad_bias), None where not
+    needed (at least one must be; without q / weight / bias theirs are always None)."""
+    B, C1, C2, N, K, G = _req_relu_group_norm(q, k, weight, bias, num_groups)
+    _req(grad_y, "grad_y", torch.float32)
+    if tuple(grad_y.shape) != (B, C1 + C2, N, K):
+        raise RuntimeError("grad_y must have shape (B, C1 + C2, N, K) = %s, got %s"
+                           % ((B, C1 + C2, N, K), tuple(grad_y.shape)))
+    for t, name in ((mean, "mean"), (rstd, "rstd")):
+        _req(t, name, torch.float32)
+        if tuple(t.shape) != (B, G):
+            raise RuntimeError("%s must have shape (B, G) = (%d, %d), got %s" % (name, B, G, tuple(t.shape)))
+    _same_device(k, grad_y, mean, rstd)
+    gq = torch.empty_like(q) if need_q and C1 > 0 else None
+    gk = torch.empty_like(k) if need_k else None
+    gw = torch.empty_like(weight) if need_weight and weight is not None else None
+    gb = torch.empty_like(bias) if need_bias and bias is not None else None
+    ws = _relu_group_norm_workspace(B, C1, C2, N, K, G, k.device)
+    with torch.cuda.device(k.device):
+        _lib.check(_lib.load().pdr_relu_group_norm_cf_grad(_ptr(q), k.data_ptr(), _ptr(weight), _ptr(bias),
+                                                           mean.data_ptr(), rstd.data_ptr(), grad_y.data_ptr(), B, C1,
+                                                           C2, N, K, G, _ptr(gq), _ptr(gk), _ptr(gw), _ptr(gb),
+                                                           ws.data_ptr(), _stream()), "relu_group_norm_grad")
+    return gq, gk, gw, gb
+
+
+QUERY_GROUP_USE_XYZ, QUERY_GROUP_ABS, QUERY_GROUP_CENTER = 1, 2, 4     # the `flags` bits of pdr_query_group_cf
 
 
 def query_group_flags(use_xyz, include_abs_coordinate=False, include_center_coordinate=False):

@@ -12,7 +12,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _ext
-from .pointnet2_utils import attention_pool, group_norm_act
+from .pointnet2_utils import attention_pool, group_norm_act, relu_group_norm
 
 
 class MyGroupNorm(nn.Module):
@@ -113,13 +113,45 @@ class AttentionModule(nn.Module):
                 tail.append(nn.ReLU(inplace=True))
             self.feat_out_conv = NormActSequential(*tail)
 
+    def score_head(self, feat, grouped_feat):
+        """feat (B,C_in1,N), grouped_feat (B,C_in2,N,K) -> scores (B,C_out,N,K): weight_conv over
+        [feat_conv(query) repeated over K | grouped_feat_conv(key)]."""
+        K = grouped_feat.shape[-1]
+        if _ext._fused_score_norm:                        # read directly: with the switch off this path calls nothing
+            scores = self._fused_score_head(feat, grouped_feat)
+            if scores is not None:
+                return scores
+        q = self.feat_conv(feat.unsqueeze(-1)).expand(-1, -1, -1, K)
+        k = self.grouped_feat_conv(grouped_feat)
+        return self.weight_conv(torch.cat([q, k], dim=1))
+
+    def _fused_score_head(self, feat, grouped_feat):
+        """The score head without the expand and the cat, each [ReLU, MyGroupNorm] pair of weight_conv as one
+        `relu_group_norm` op (set_fused_score_norm, default off); None where that does not apply: no norms
+        (attention_bn=False), tensors that are not fp32 on the GPU, or a shape the kernels do not take."""
+        wc = self.weight_conv
+        if len(wc) != 6 or not (isinstance(wc[1], MyGroupNorm) and isinstance(wc[4], MyGroupNorm)):
+            return None
+        if not (feat.is_cuda and grouped_feat.is_cuda and feat.dtype == torch.float32
+                and grouped_feat.dtype == torch.float32 and feat.dim() == 3 and grouped_feat.dim() == 4):
+            return None
+        B, _, N, K = grouped_feat.shape
+        C1, C2 = self.feat_conv.out_channels, self.grouped_feat_conv.out_channels
+        if not (_ext.relu_group_norm_supported(C1, (B, C2, N, K), wc[1].num_groups)
+                and _ext.relu_group_norm_supported(0, (B, wc[2].out_channels, N, K), wc[4].num_groups)):
+            return None
+        q = self.feat_conv(feat.unsqueeze(-1)).squeeze(-1)
+        k = self.grouped_feat_conv(grouped_feat)
+        gn = wc[1].group_norm
+        h = wc[2](relu_group_norm(k, gn.weight, gn.bias, wc[1].num_groups, gn.eps, q=q))
+        gn = wc[4].group_norm
+        return wc[5](relu_group_norm(h, gn.weight, gn.bias, wc[4].num_groups, gn.eps))
+
     def forward(self, feat, grouped_feat, grouped_feat_out, count):
         """feat (B,C_in1,N) query; grouped_feat (B,C_in2,N,K) key; grouped_feat_out (B,C_out,N,K)
         value; count (B,N) valid neighbours or 'all'.  Returns (B,C_out,N)."""
         K = grouped_feat.shape[-1]
-        q = self.feat_conv(feat.unsqueeze(-1)).expand(-1, -1, -1, K)
-        k = self.grouped_feat_conv(grouped_feat)
-        scores = self.weight_conv(torch.cat([q, k], dim=1))
+        scores = self.score_head(feat, grouped_feat)
         if _ext.is_fused_attention_pool() and _fusable(scores, grouped_feat_out):
             # one launch forward, one backward, no saved softmax (pdr_attention_pool_cf); the switch is off by default
             if self.transform_grouped_feat_out:

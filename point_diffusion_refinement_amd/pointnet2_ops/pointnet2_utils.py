@@ -202,6 +202,42 @@ def group_norm_act(x, weight, bias, num_groups, eps=1e-5, act='none'):
     return GroupNormAct.apply(x.contiguous(), weight, bias, num_groups, eps, act)
 
 
+class ReluGroupNorm(Function):
+    """MyGroupNorm(relu([q over K | k])): _ext.relu_group_norm.  Saves q, k, weight, bias and the (B, G) mean / rstd --
+    neither the cat nor y; the backward recomputes the normalised values from them and is order-fixed."""
+
+    @staticmethod
+    def forward(ctx, q, k, weight, bias, num_groups, eps):
+        y, mean, rstd = _ext.relu_group_norm(q, k, weight, bias, num_groups, eps)
+        ctx.num_groups, ctx.has_q, ctx.affine = num_groups, q is not None, weight is not None
+        ctx.save_for_backward(*[t for t in (k, mean, rstd, q, weight, bias) if t is not None])
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_y):
+        saved = list(ctx.saved_tensors)
+        k, mean, rstd = saved[:3]
+        q = saved[3] if ctx.has_q else None
+        weight, bias = saved[-2:] if ctx.affine else (None, None)
+        need_q = ctx.has_q and ctx.needs_input_grad[0]
+        need_k = ctx.needs_input_grad[1]
+        need_w, need_b = (ctx.needs_input_grad[2], ctx.needs_input_grad[3]) if ctx.affine else (False, False)
+        if not (need_q or need_k or need_w or need_b):
+            return None, None, None, None, None, None
+        gq, gk, gw, gb = _ext.relu_group_norm_grad(q, k, weight, bias, mean, rstd, grad_y.contiguous().float(),
+                                                   ctx.num_groups, need_q, need_k, need_w, need_b)
+        return gq, gk, gw, gb, None, None
+
+
+def relu_group_norm(k, weight, bias, num_groups, eps=1e-5, q=None):
+    """k (B, C2, N, K) f32 on the GPU, q (B, C1, N) or None, weight / bias (C - C % num_groups) or both None,
+    C = C1 + C2 -> MyGroupNorm(relu(cat([q expanded over K, k], 1))) (B, C, N, K) as one differentiable op
+    (pdr_relu_group_norm_cf / pdr_relu_group_norm_cf_grad): the ReLU-then-norm links of AttentionModule.weight_conv,
+    the first one without its expand and cat.  The trailing C % num_groups channels are not normalised."""
+    return ReluGroupNorm.apply(None if q is None else q.contiguous(), k.contiguous(), weight, bias, num_groups, eps)
+
+
 class QueryGroup(Function):
     """xyz (B,n,3), new_xyz (B,m,3), features (B,C,n) | None, idx (B,m,K) i32, counts (B,m) i32 | None, flags ->
     (B, C + 3E, m, K): _ext.query_group.  Saves idx and counts only -- every output value is a copy or one difference
