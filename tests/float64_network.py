@@ -13,6 +13,19 @@ continuous, so what separates an fp32 evaluation from this one is rounding -- kn
     record_modules(net)      forward hooks -> per call {module name: (B, n, C) tensor} (+ "eps")
     record_fused(fused)      the same for FusedCloudConditionNet, keyed by the name of the module a block was built from
     log_indices()            the integer outputs of the index ops that are installed when it is entered
+
+A whole training step (forward, loss, backward) is evaluated the same way.  `float64_ops` also covers the backward
+entries the autograd Functions of pointnet2_utils.py call, so `loss.backward()` runs through the swap.  Two kinds of
+decision are left once the geometry is shared, and a gradient is only comparable when they are shared too:
+
+    relu_tape("record")        the ReLU masks of a forward, one per site in call order -- the fused entries that hold a
+    relu_tape("replay", tape)  ReLU record the same sites as the composition -- and their replay in another
+                               evaluation (the float64 model under the masks of the fp32 run it is the reference of)
+    record_max_gaps(net)       the two max-over-points of the global PointNet are NOT pinned; this measures how far
+                               each of them is from a tie, so a test can assert that no evaluation can pick another point
+    coordinate_leaf(net, x)    a leaf in place of the level-0 coordinates (forward() cuts the graph at its input)
+    count_ext_calls(net)       counters, block attribution and result editing for the ten fused `_ext` entries
+    block_of(parameter name)   the top-level block a parameter belongs to
 """
 import contextlib
 import copy
@@ -28,7 +41,16 @@ from point_diffusion_refinement_amd.pointnet2_ops import _ext
 INDEX_OPS = ("furthest_point_sampling", "ball_query", "knn_points", "three_nn")
 # switches and shape predicates of `_ext` that launch nothing: left in place
 _PASS_THROUGH = {"set_deterministic", "is_deterministic", "set_fused_attention_pool", "is_fused_attention_pool",
-                 "set_fused_group_norm", "is_fused_group_norm", "attention_pool_supported", "group_norm_act_supported"}
+                 "set_fused_group_norm", "is_fused_group_norm", "attention_pool_supported", "group_norm_act_supported",
+                 "set_fused_grouping", "is_fused_grouping", "set_fused_knn_grouping", "is_fused_knn_grouping",
+                 "set_fused_score_norm", "is_fused_score_norm"}
+# the five one-op switches of the module path, and the `_ext` entries (forward, backward) each of them reaches
+SWITCHES = ("attention_pool", "group_norm", "grouping", "knn_grouping", "score_norm")
+FUSED_ENTRIES = {"attention_pool": ("attention_pool", "attention_pool_grad"),
+                 "group_norm": ("group_norm_act", "group_norm_act_grad"),
+                 "grouping": ("query_group", "query_group_grad"),
+                 "knn_grouping": ("knn_group_cf", "knn_group_cf_grad"),
+                 "score_norm": ("relu_group_norm", "relu_group_norm_grad")}
 # the children of PointNet2CloudCondition whose outputs are recorded, and the fused network's lists built from them
 BLOCK_LISTS = (("SA_modules", "sa"), ("FP_modules", "fp"), ("encoder_feature_map", "enc_map"),
                ("decoder_feature_map", "dec_map"), ("SA_modules_condition", "cond_sa"),
@@ -96,6 +118,20 @@ def _three_interpolate(points, idx, weight):
     return (_group_points(points, idx) * weight.to(points.dtype).unsqueeze(1)).sum(-1)
 
 
+def _scatter_points_grad(grad_out, idx, n):
+    """Backward of _gather_points / _group_points: (B, C, m) or (B, C, np, ns), idx (B, m) or (B, np, ns), n ->
+    (B, C, n) in grad_out's dtype.  Indices are taken as the forward takes them (`idx.long()`, no padding slot: ball
+    query pads with a real index, and a negative one raises here as it does there)."""
+    B, C = grad_out.shape[:2]
+    flat = idx.reshape(B, 1, -1).long().expand(-1, C, -1)
+    return grad_out.new_zeros(B, C, int(n)).scatter_add_(2, flat, grad_out.reshape(B, C, -1))
+
+
+def _three_interpolate_grad(grad_out, idx, weight, m):
+    """Backward of _three_interpolate w.r.t. points: (B, C, n), (B, n, 3), (B, n, 3), m -> (B, C, m)."""
+    return _scatter_points_grad(grad_out.unsqueeze(-1) * weight.to(grad_out.dtype).unsqueeze(1), idx, m)
+
+
 def _table(index):
     def furthest_point_sampling(points, nsamples):
         return index["fps"](points, int(nsamples)).to(torch.int32)
@@ -115,9 +151,14 @@ def _table(index):
         idx = index["three_nn"](unknowns, knows).to(torch.int32)
         return [_sq_dists(unknowns, knows, idx)[0], idx]
 
-    return {"furthest_point_sampling": furthest_point_sampling, "ball_query": ball_query, "knn_points": knn_points,
-            "three_nn": three_nn, "gather_points": _gather_points, "group_points": _group_points,
-            "three_interpolate": _three_interpolate}
+    table = {"furthest_point_sampling": furthest_point_sampling, "ball_query": ball_query, "knn_points": knn_points,
+             "three_nn": three_nn, "gather_points": _gather_points, "group_points": _group_points,
+             "three_interpolate": _three_interpolate}
+    for suffix in ("", "_det"):                      # one scatter-add each: a fixed order has nothing to add in double
+        table["gather_points_grad" + suffix] = _scatter_points_grad
+        table["group_points_grad" + suffix] = _scatter_points_grad
+        table["three_interpolate_grad" + suffix] = _three_interpolate_grad
+    return table
 
 
 def _uncovered(name):
@@ -128,10 +169,14 @@ def _uncovered(name):
 
 
 @contextlib.contextmanager
-def float64_ops(index_ops, f32_step_embedding=True):
+def float64_ops(index_ops, f32_step_embedding=True, dtype=torch.float64):
     """Swap `pointnet2_ops._ext` for the float64 evaluation: index ops by `index_ops` ("oracle" | "hip") on the fp32
-    cast of their coordinates, data-moving ops as torch indexing in their input's dtype, returned distances recomputed
+    cast of their coordinates, data-moving ops and their backward entries (gather / group / three_interpolate `_grad`
+    and `_grad_det`, one scatter-add each) as torch indexing in their input's dtype, returned distances recomputed
     in the input dtype from the chosen indices; every other kernel entry of `_ext` raises.
+
+    dtype: what the step embedding is cast to, i.e. the dtype of the model that runs inside.  The stand-ins follow
+    their inputs, so `dtype=torch.float32` carries the fp32 module through the same table: the composition on the CPU.
 
     f32_step_embedding: `calc_t_emb` evaluates ts * freq in f32 and takes sin / cos of that f32 product; the fused
     pdr_embed_linear reproduces this on purpose, so it is the specification: the float64 model takes the f32 result cast
@@ -151,9 +196,9 @@ def float64_ops(index_ops, f32_step_embedding=True):
     assert set(table) <= set(saved), sorted(set(table) - set(saved))
     calc = _model.calc_t_emb
     if f32_step_embedding:
-        _model.calc_t_emb = lambda ts, dim: calc(ts.to(torch.float32), dim).to(torch.float64)
+        _model.calc_t_emb = lambda ts, dim: calc(ts.to(torch.float32), dim).to(dtype)
     else:
-        _model.calc_t_emb = lambda ts, dim: calc(ts.to(torch.float64), dim).to(torch.float64)
+        _model.calc_t_emb = lambda ts, dim: calc(ts.to(torch.float64), dim).to(dtype)
     try:
         yield
     finally:
@@ -165,9 +210,11 @@ def float64_ops(index_ops, f32_step_embedding=True):
 @contextlib.contextmanager
 def log_indices():
     """Record the integer outputs of the index ops installed right now (enter it INSIDE oracle_ops / float64_ops, or
-    alone around the real kernels) -> list of (op name, tensor on the CPU), in call order."""
+    alone around the real kernels) -> list of (op name, tensor on the CPU), in call order.  `_ext.knn_group`, the
+    search `group_knn` takes instead of `knn_points` under set_fused_knn_grouping, is logged under the name
+    "knn_points": the same decision at the same place in the call order (int32 there, int64 here)."""
     log = []
-    saved = {k: getattr(_ext, k) for k in INDEX_OPS}
+    saved = {k: getattr(_ext, k) for k in INDEX_OPS + ("knn_group",)}
 
     def wrap(name, fn):
         def logged(*a, **k):
@@ -178,7 +225,7 @@ def log_indices():
             return out
         return logged
     for name, fn in saved.items():
-        setattr(_ext, name, wrap(name, fn))
+        setattr(_ext, name, wrap("knn_points" if name == "knn_group" else name, fn))
     try:
         yield log
     finally:
@@ -191,6 +238,217 @@ def float64_model(net):
     m = copy.deepcopy(net)
     m.reset_cond_features()
     return m.double().eval()
+
+
+# ------------------------------------------------------------------------------------------------ ReLU decisions
+class ReluTape:
+    """`masks`: one bool tensor (x > 0) per ReLU site of a forward, in call order; `kinds`: what recorded each
+    ("relu" = an nn.ReLU module, "group_norm_act" / "relu_group_norm" = the fused entry that holds the ReLU)."""
+
+    def __init__(self, masks=(), kinds=()):
+        self.masks, self.kinds = list(masks), list(kinds)
+
+    def __len__(self):
+        return len(self.masks)
+
+    def shapes(self):
+        return [tuple(m.shape) for m in self.masks]
+
+    def elements(self):
+        return sum(m.numel() for m in self.masks)
+
+    def differing(self, other):
+        """Number of mask elements on which two tapes of the same sites disagree."""
+        assert self.shapes() == other.shapes()
+        return sum(int((a != b.to(a.device)).sum()) for a, b in zip(self.masks, other.masks))
+
+    def flipped(self, site, index):
+        """A copy with one element of one site inverted (`index`: a tuple into that site's mask)."""
+        masks = list(self.masks)
+        masks[site] = masks[site].clone()
+        masks[site][index] = ~masks[site][index]
+        return ReluTape(masks, self.kinds)
+
+
+@contextlib.contextmanager
+def relu_tape(mode, tape=None):
+    """Pin the ReLU decisions of a forward, as the index ops pin the geometric ones.  A mask that differs between two
+    evaluations is a decision, not rounding: the float64 gradient then belongs to another piecewise-linear function.
+
+    mode "record": every nn.ReLU call (the in-place modules too, evaluated out of place) appends `x > 0` to a new tape
+    and returns `x * mask`; the two fused `_ext` entries that contain a ReLU append the mask of the same virtual site:
+    `group_norm_act(act="relu")` that of its output, `relu_group_norm(q, k)` that of cat([q over K, k], 1) -- the tensor
+    the composition rectifies at weight_conv[0] / weight_conv[3].  A fused run and the composition therefore record
+    the same sites in the same order.  Yields the tape.
+    mode "replay": every nn.ReLU call consumes the next mask of `tape` (same shape, or an AssertionError that names
+    the site) and returns `x * mask`; leaving the context with masks left over is an error too.  Swish, the masked
+    softmax and the integer clamp of counts hold no such decision."""
+    if mode not in ("record", "replay") or (mode == "replay") != (tape is not None):
+        raise ValueError("relu_tape('record') or relu_tape('replay', tape)")
+    relu_forward = torch.nn.ReLU.forward
+    fused = {"group_norm_act": _ext.group_norm_act, "relu_group_norm": _ext.relu_group_norm}
+    pos = [0]
+    if mode == "record":
+        tape = ReluTape()
+
+        def forward(self, x):
+            mask = x > 0
+            tape.masks.append(mask)
+            tape.kinds.append("relu")
+            return x * mask.to(x.dtype)
+
+        def group_norm_act(x, weight, bias, num_groups, eps=1e-5, act="none"):
+            out = fused["group_norm_act"](x, weight, bias, num_groups, eps, act)
+            if act == "relu":
+                tape.masks.append(out[0] > 0)
+                tape.kinds.append("group_norm_act")
+            return out
+
+        def relu_group_norm(q, k, *a, **kw):
+            mask = k > 0
+            if q is not None:
+                mask = torch.cat([(q > 0).unsqueeze(-1).expand(-1, -1, -1, k.shape[3]), mask], 1)
+            tape.masks.append(mask)
+            tape.kinds.append("relu_group_norm")
+            return fused["relu_group_norm"](q, k, *a, **kw)
+
+        _ext.group_norm_act, _ext.relu_group_norm = group_norm_act, relu_group_norm
+    else:
+        def forward(self, x):
+            site = pos[0]
+            assert site < len(tape), "relu_tape: ReLU call %d, the tape holds %d sites" % (site, len(tape))
+            mask = tape.masks[site]
+            assert mask.shape == x.shape, "relu_tape: site %d (%s) was recorded with shape %s, replayed on %s" % (
+                site, tape.kinds[site], tuple(mask.shape), tuple(x.shape))
+            pos[0] += 1
+            return x * mask.to(device=x.device, dtype=x.dtype)
+    torch.nn.ReLU.forward = forward
+    try:
+        yield tape
+        if mode == "replay":
+            assert pos[0] == len(tape), "relu_tape: the replay ended at site %d of %d" % (pos[0], len(tape))
+    finally:
+        torch.nn.ReLU.forward = relu_forward
+        _ext.group_norm_act, _ext.relu_group_norm = fused["group_norm_act"], fused["relu_group_norm"]
+
+
+@contextlib.contextmanager
+def coordinate_leaf(net, x):
+    """A gradient w.r.t. the coordinates of x_t.  `PointNet2CloudCondition.forward` splits its input under
+    `torch.no_grad()` (as the reference does), so `x.requires_grad_()` reaches no op and `x.grad` stays None.  Here one
+    leaf with x's values stands in for the level-0 coordinates wherever a recorded block receives them (the first
+    encoder / last decoder feature map as queries, SA_modules.0 as the cloud, FP_modules.0 as the unknowns); the deeper
+    levels are gathers of it.  That gradient runs through the coordinate paths of the grouping ops: relative and centre
+    channels, kNN distances, weights.  The copy of the coordinates in the input features stays a constant, in every
+    evaluation alike.  x: (B, N, 3) in the dtype the network sees.  Yields the leaf."""
+    leaf = x.detach().clone().requires_grad_()
+
+    def swap(t):
+        same = torch.is_tensor(t) and t.shape == leaf.shape and t.dtype == leaf.dtype and not t.requires_grad
+        return leaf if same and torch.equal(t, leaf.detach()) else t
+
+    def hook(module, args, kwargs):
+        return tuple(swap(t) for t in args), {k: swap(v) for k, v in kwargs.items()}
+    handles = [m.register_forward_pre_hook(hook, with_kwargs=True) for m in module_names(net).values()]
+    try:
+        yield leaf
+    finally:
+        for h in handles:
+            h.remove()
+
+
+@contextlib.contextmanager
+def record_max_gaps(net):
+    """The two max-over-points reductions of the global PointNet (models/pnet.py) are argmax decisions that nothing
+    pins.  Forward hooks on `global_pnet.mlp1` / `.mlp2` -> {name: (smallest gap, dead columns)} per forward: the gap
+    between the largest and the second-largest value of a reduced column over the tensor's largest magnitude, the
+    minimum over the columns; a column whose largest value is exactly 0 behind a ReLU (every point rectified away, all
+    of them tied at 0) is counted as dead and left out: its mask is pinned, so every evaluation has the same zeros there
+    and whichever point the max picks passes a gradient that the mask then removes."""
+    gaps = {}
+
+    def hook(name):
+        def record(m, args, out):
+            t = out.detach()
+            top = t.topk(2, dim=2).values                                   # (B, C, 2, 1)
+            dead = (top[:, :, 0] == 0) & (top[:, :, 1] == 0)
+            gap = ((top[:, :, 0] - top[:, :, 1]) / t.abs().max()).masked_fill(dead, float("inf"))
+            gaps[name] = (float(gap.min()), int(dead.sum()))
+        return record
+    handles = [getattr(net.global_pnet, k).register_forward_hook(hook("global_pnet." + k)) for k in ("mlp1", "mlp2")]
+    try:
+        yield gaps
+    finally:
+        for h in handles:
+            h.remove()
+
+
+# ------------------------------------------------------------------------------------------------ fused-entry calls
+# position of the saved tensor that ties a backward call to its forward call: (forward entry, arg) / (backward, arg)
+_CALL_KEYS = {"attention_pool": 0, "attention_pool_grad": 0, "group_norm_act": 0, "group_norm_act_grad": 0,
+              "relu_group_norm": 1, "relu_group_norm_grad": 1, "query_group": 3, "query_group_grad": 0,
+              "knn_group_cf": 3, "knn_group_cf_grad": 2}
+
+
+class ExtCalls:
+    """`log`: (entry, block, differentiable) per call of a fused `_ext` entry, in call order -- block = the recorded
+    child of the network the call belongs to, differentiable = a floating input required a gradient (forward entries).
+    `edit[entry] = fn(n, block, out) -> out` rewrites the n-th result of an entry (fault seeding, in Python)."""
+
+    def __init__(self):
+        self.log, self.edit = [], {}
+
+    def count(self, entry, block="*"):
+        """Calls of `entry`, in all blocks or in one (None: outside every recorded block)."""
+        return sum(1 for e, b, _ in self.log if e == entry and (block == "*" or b == block))
+
+    def differentiable(self, entry):
+        return sum(1 for e, _, d in self.log if e == entry and d)
+
+
+@contextlib.contextmanager
+def count_ext_calls(net):
+    """Wrap the ten fused entries of `_ext` (FUSED_ENTRIES) with counters for one network -> ExtCalls.  A forward call
+    is attributed to the recorded block whose forward is running, a backward call to the block of the forward call
+    that saved the same tensor."""
+    calls, stack, owner = ExtCalls(), [], {}
+    saved = {e: getattr(_ext, e) for pair in FUSED_ENTRIES.values() for e in pair}
+
+    def wrap(entry, fn):
+        def wrapped(*a, **k):
+            out = fn(*a, **k)
+            key = a[_CALL_KEYS[entry]].data_ptr()
+            if entry.endswith("_grad"):
+                block, diff = owner.get(key), False
+            else:
+                block = owner[key] = stack[-1] if stack else None
+                diff = any(torch.is_tensor(t) and t.is_floating_point() and t.requires_grad for t in a)
+            n = calls.count(entry)
+            calls.log.append((entry, block, diff))
+            return calls.edit[entry](n, block, out) if entry in calls.edit else out
+        return wrapped
+    def leave(m, args, out):
+        stack.pop()
+    handles = []
+    for name, mod in module_names(net).items():
+        handles.append(mod.register_forward_pre_hook(lambda m, args, name=name: stack.append(name)))
+        handles.append(mod.register_forward_hook(leave))
+    for entry, fn in saved.items():
+        setattr(_ext, entry, wrap(entry, fn))
+    try:
+        yield calls
+    finally:
+        for entry, fn in saved.items():
+            setattr(_ext, entry, fn)
+        for h in handles:
+            h.remove()
+
+
+def block_of(name):
+    """Top-level block of a parameter name: 'SA_modules.0.mlps.0.fc.weight' -> 'SA_modules.0', 'fc_t1.weight' ->
+    'fc_t1', 'fc_lyaer.3.bias' -> 'fc_lyaer': the recorded blocks of `module_names`, and the network's other children."""
+    parts = name.split(".")
+    return ".".join(parts[:2]) if parts[0] in {attr for attr, _ in BLOCK_LISTS} else parts[0]
 
 
 # ------------------------------------------------------------------------------------------------ recorders

@@ -1,0 +1,137 @@
+"""TEST INFRASTRUCTURE: one training step of the tiny network (forward, MSE loss, backward, no optimiser), its float64
+reference with pinned ReLU decisions, and the judge -- shared by tests/test_train_step_f64_host.py (CPU) and
+tests/test_train_step_f64_gpu.py.
+
+Error measure (the project's, tests/test_group_norm_act_gpu.py `judge`): e(t) = max |got - want| / scale, scale = the
+largest float64 element of the tensor -- or, for a parameter gradient whose float64 reference is below 1e-3 of the
+largest gradient element of the network (exactly zero in exact arithmetic, such as a bias in front of a GroupNorm), that
+largest element.  A forward record (tests/float64_network.py `record_modules`) is a tensor like any other.
+"""
+import statistics
+
+import torch
+
+from tests import float64_network as F64
+from tests.golden.det_weights import fill_deterministic
+from tests.golden.tiny_config import tiny_pointnet_config
+
+from point_diffusion_refinement_amd.pointnet2.models.pointnet2_with_pcld_condition import PointNet2CloudCondition
+
+B, N, M = 2, 128, 192                          # clouds, points of x_t, points of the condition (192 x 4)
+TS, LABELS = (500.0, 20.0), (1, 7)
+FACTOR = 4.0                                   # the project's rule: switch on <= 4 x switch off
+GAP_BOUND = 1e-4                               # smallest top-1 / top-2 gap of the unpinned max-over-points (A3)
+
+# name -> (activation, regime, input seed).  The seeds are those whose float64 run keeps every max-over-points at least
+# GAP_BOUND from a tie (test_max_over_points_is_far_from_a_tie; judged on the float64 run alone).
+# The max depends on the condition cloud only, i.e. on the seed: of the seeds 1 .. 10, 3, 9 and 10 pass (smallest gaps
+# 2.2e-4, 1.7e-4, 1.4e-4); 5, the seed of the other host tests, does not (1.0e-5).
+CASES = {"relu-noise": ("relu", "noise", 3), "relu-surface": ("relu", "surface", 9), "swish-noise": ("swish", "noise", 10)}
+
+# E_cpu: the pinned error of the fp32 composition ON THE CPU against float64, per case: the largest over the 837
+# parameter gradients, over the 26 block records, and at the output.  It moves with the summation order of the host's
+# convolutions: measured with 1, 3 and 8 threads, the largest of the three was (1.89e-4, 2.25e-5, 1.15e-5),
+# (3.31e-4, 2.87e-5, 1.47e-5) and (4.33e-5, 4.66e-6, 1.61e-6), the smallest 0.55 of that.  E is that largest figure
+# times 1.3, rounded up; test_cpu_baseline keeps it honest (the measurement must lie within [E / 8, E]); the GPU test
+# caps the error of the GPU composition at 4 E.
+E_CPU = {"relu-noise": (2.5e-4, 3.0e-5, 1.5e-5), "relu-surface": (4.4e-4, 3.8e-5, 2.0e-5),
+         "swish-noise": (5.7e-5, 6.2e-6, 2.2e-6)}
+
+
+def network(activation):
+    cfg = tiny_pointnet_config()
+    cfg["activation"] = activation
+    return fill_deterministic(PointNet2CloudCondition(cfg), 21).eval()
+
+
+def inputs(regime, seed):
+    """-> x (B, N, 3), condition (B, M, 4), target (B, N, 3), ts, label: fp32 / int64 on the CPU.  noise: x ~ N(0, 1);
+    surface: the first N condition points + 0.01 randn."""
+    g = torch.Generator().manual_seed(seed)
+    x = torch.randn(B, N, 3, generator=g)
+    cond = torch.cat([torch.rand(B, M, 3, generator=g) * 2 - 1, torch.ones(B, M, 1)], 2)
+    target = torch.randn(B, N, 3, generator=g)
+    if regime == "surface":
+        x = (cond[:, :N, :3] + 0.01 * x).contiguous()
+    else:
+        assert regime == "noise"
+    return x, cond, target, torch.tensor(TS), torch.tensor(LABELS)
+
+
+def step(model, data, leaf=False):
+    """One step of `model` on `data` (as `inputs` returns it, on the model's device; floats are cast to the model's
+    dtype) -> {"out": (B, N, 3), "grads": {parameter name: tensor, "x": coordinate gradient if `leaf`},
+    "records": {block: tensor}}, everything detached, double, on the CPU."""
+    x, cond, target, ts, label = data
+    dtype = next(model.parameters()).dtype
+    model.zero_grad(set_to_none=True)
+    model.reset_cond_features()
+    x = x.to(dtype)
+    with F64.record_modules(model) as rec:
+        if leaf:
+            with F64.coordinate_leaf(model, x) as x_leaf:
+                out = model(x, cond.to(dtype), ts=ts, label=label)
+        else:
+            out = model(x, cond.to(dtype), ts=ts, label=label)
+    loss = ((out - target.to(dtype)) ** 2).mean()
+    loss.backward()
+    grads = {n: (None if p.grad is None else p.grad.detach().double().cpu()) for n, p in model.named_parameters()}
+    if leaf:
+        grads["x"] = None if x_leaf.grad is None else x_leaf.grad.detach().double().cpu()
+    model.zero_grad(set_to_none=True)
+    records = {k: v.double().cpu() for k, v in rec.calls[-1].items() if k != "eps"}
+    return {"out": out.detach().double().cpu(), "grads": grads, "records": records}
+
+
+def errors(got, want):
+    """-> {"out": e, "grad:<name>": e, "record:<block>": e} of one step against its float64 reference."""
+    top = max(float(w.abs().max()) for n, w in want["grads"].items() if n != "x")
+    e = {"out": float((got["out"] - want["out"]).abs().max()) / float(want["out"].abs().max())}
+    for n, w in want["grads"].items():
+        scale = float(w.abs().max())
+        if scale < 1e-3 * top:
+            scale = top
+        e["grad:" + n] = float((got["grads"][n] - w).abs().max()) / scale
+    for n, w in want["records"].items():
+        e["record:" + n] = float((got["records"][n] - w).abs().max()) / float(w.abs().max())
+    return e
+
+
+def block(tensor_name):
+    """The top-level block of a judged tensor: 'grad:SA_modules.0.mlps.0.fc.weight' and 'record:SA_modules.0' ->
+    'SA_modules.0'; 'out' -> 'eps'; 'grad:x' -> 'x'."""
+    kind, _, name = tensor_name.partition(":")
+    return "eps" if kind == "out" else F64.block_of(name)
+
+
+def floors(e_off):
+    """m_off per block: the median e(off, .) over the parameter gradients of the same top-level block."""
+    by_block = {}
+    for t, e in e_off.items():
+        if t.startswith("grad:"):
+            by_block.setdefault(block(t), []).append(e)
+    return {b: statistics.median(v) for b, v in by_block.items()}
+
+
+def judge(e_on, e_off):
+    """The rule, per parameter gradient and per block record: e(S, t) <= FACTOR * max(e(off, t), m_off(block of t)).
+    The floor keeps a tensor whose composition error happened to be small from failing at a typical error: the
+    error of a tensor is a maximum over its elements, one draw per evaluation, and e(off, t) of a single tensor can lie
+    several times below its neighbours'.  The output belongs to no block with gradients of its own scale and stands
+    alone: its floor is its own e(off).  -> [(tensor, block, e_on, bound)] of the tensors above their bound, and the
+    largest e_on / bound."""
+    m_off = floors(e_off)
+    failed, worst = [], (0.0, None)
+    for t, e in e_on.items():
+        bound = FACTOR * max(e_off[t], m_off.get(block(t), 0.0))
+        if not e <= bound:
+            failed.append((t, block(t), e, bound))
+        if bound > 0 and e / bound > worst[0]:
+            worst = (e / bound, t)
+    return failed, worst
+
+
+def summary(e):
+    """(largest gradient error, largest record error, output error) of an `errors` dict."""
+    return (max(v for k, v in e.items() if k.startswith("grad:")), max(v for k, v in e.items() if k.startswith("record:")),
+            e["out"])
