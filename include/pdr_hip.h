@@ -73,7 +73,7 @@ typedef void *pdr_stream_t; /* hipStream_t */
  *                pdr_query_group_cf / pdr_query_group_cf_grad are new; pdr_knn_group_cf_workspace_bytes /
  *                pdr_knn_group_cf_plan / pdr_knn_group_cf / pdr_knn_group_cf_grad are new;
  *                pdr_relu_group_norm_cf_workspace_bytes / pdr_relu_group_norm_cf_plan / pdr_relu_group_norm_cf /
- *                pdr_relu_group_norm_cf_grad are new. */
+ *                pdr_relu_group_norm_cf_grad are new; pdr_group_norm_act_add / pdr_group_norm_act_add_grad are new. */
 int pdr_version(void);
 /* last hip error string seen by this thread after a PDR_ELAUNCH ("" if none) */
 const char *pdr_last_error(void);
@@ -426,6 +426,31 @@ size_t pdr_group_norm_act_workspace_bytes(int B, int C, long S, int G);
  * aligned.  out = {family (0 scalar, 1 vector), partitions per slab P, elements per partition E, Cg}.
  * C, S or G <= 0, C < G or a NULL out: PDR_EINVAL; C S >= 2^31: PDR_EUNSUPPORTED. */
 int pdr_group_norm_act_plan(int C, long S, int G, int aligned16, long out[4]);
+/* pdr_group_norm_act with what Mlp_plus_t_emb adds behind a [conv, MyGroupNorm, act] stack folded into the apply
+ * kernel: an embedding add (B,C) f32 broadcast over S and a residual (B,C,S) f32 dense, each may be NULL,
+ *     y = fl(fl(act(z) + add[b,c]) + residual[b,c,s])     the composition's order; a NULL term is skipped.
+ * Everything else is pdr_group_norm_act's: the same two launches, statistics, operation chain, summation order,
+ * workspace, properties and validation (the sizes first, in the same order, then the pointers; add and residual are
+ * optional, so they add no failure).  mean and rstd have pdr_group_norm_act's bits, y has the bits of its y followed
+ * by the two fp32 additions, and with add == residual == NULL the call launches that entry's kernels.  A NaN or an
+ * infinity in add / residual propagates as an fp32 addition propagates it.  The vector family also needs residual
+ * 16-byte aligned. */
+int pdr_group_norm_act_add(const float *x, const float *gamma, const float *beta, const float *add,
+                           const float *residual, int B, int C, long S, int G, float eps, int act, float *y,
+                           float *mean, float *rstd, void *workspace, pdr_stream_t stream);
+/* Backward of pdr_group_norm_act_add.  It reads neither add nor residual: d y / d act(z) = 1, so grad_x, grad_gamma and
+ * grad_beta are pdr_group_norm_act_grad's on the same grad_y, bit for bit; the residual's gradient is grad_y itself
+ * (no kernel; the caller returns it); and
+ *     grad_add[b,c] = float(sum_s double(grad_y[b,c,s]))   (B,C) f32, the RAW grad_y, pass-through rows included,
+ * summed in double in the row order (thread t of 256 takes elements (256 i + t) V .. + V - 1, i ascending, then the
+ * lane butterfly, the four waves ascending), rounded once and written by the row kernel: the same THREE launches and
+ * the same workspace as pdr_group_norm_act_grad.  Each of the four gradients may be NULL; all four NULL: PDR_EINVAL.
+ * No atomics, no allocation, no synchronisation: capturable; the same input gives the same bits, and cloud b of a
+ * batched call has the bits of the B = 1 call on that cloud (grad_gamma / grad_beta sum over b). */
+int pdr_group_norm_act_add_grad(const float *x, const float *gamma, const float *beta, const float *mean,
+                                const float *rstd, const float *grad_y, int B, int C, long S, int G, int act,
+                                float *grad_x, float *grad_gamma, float *grad_beta, float *grad_add, void *workspace,
+                                pdr_stream_t stream);
 /* The front of AttentionModule's score head on the TRAINABLE path (pointnet2_ops/attention.py: expand, cat, then
  * weight_conv's ReLU and MyGroupNorm -- activation FIRST, then norm) as one differentiable op over a tensor that is
  * never built:

@@ -54,6 +54,8 @@ SIGNATURES = {
     "pdr_group_norm_act_plan": (_I, [_I, _c.c_long, _I, _I, _P]),
     "pdr_group_norm_act": (_I, [_P, _P, _P, _I, _I, _c.c_long, _I, _F, _I, _P, _P, _P, _P, _P]),
     "pdr_group_norm_act_grad": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _c.c_long, _I, _I, _P, _P, _P, _P, _P]),
+    "pdr_group_norm_act_add": (_I, [_P, _P, _P, _P, _P, _I, _I, _c.c_long, _I, _F, _I, _P, _P, _P, _P, _P]),
+    "pdr_group_norm_act_add_grad": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _c.c_long, _I, _I, _P, _P, _P, _P, _P, _P]),
     "pdr_relu_group_norm_cf_workspace_bytes": (_Z, [_I, _I, _I, _I, _I, _I]),
     "pdr_relu_group_norm_cf_plan": (_I, [_I, _I, _I, _I, _I, _I, _P]),
     "pdr_relu_group_norm_cf": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _P, _P, _P, _P, _P]),

@@ -40,6 +40,19 @@
 // + 1 write of the tensor, backward 4 reads (x and dy twice) + 1 write.  S % 4 != 0 or a pointer of x / y / grad_y /
 // grad_x that is not 16-byte aligned takes the scalar family: the same kernels with 4-byte accesses.
 // NOT MEASURED: a single launch with one workgroup per slab, and other values of P / E.
+//
+// INJECTION AND RESIDUAL (pdr_group_norm_act_add / pdr_group_norm_act_add_grad): what Mlp_plus_t_emb adds
+// behind a [conv, MyGroupNorm, act] stack, e (B, C) broadcast over S and r (B, C, S), each optional, in the order of
+// the composition h + e[:, :, None] then + r:
+//     y = fl(fl(act(z) + e[b, c]) + r[b, c, s])        an absent term is skipped, not added as zero
+//   Forward: gn_stats_kernel as above; the apply kernel's ADD variant loads e[b C + c] once per workgroup (a uniform
+//   address: a scalar) and r with the family's pack width (the vector family also needs r 16-byte aligned).  Without
+//   e and r the entry launches the kernels of pdr_group_norm_act: the same bits.  Bytes: one more read with r.
+//   Backward: d y / d act(z) = 1, so grad_x, grad_gamma, grad_beta are the chain above on the same grad_y, bit for bit,
+//   and need neither e nor r; grad_r is grad_y itself (no kernel: the caller returns it);
+//     grad_e[b, c] = float(sum_s double(grad_y[b, c, s]))    the RAW grad_y, not dz, pass-through rows too
+//   summed by the row kernel's GE variant in the row order above (thread stride, butterfly, four waves ascending), in
+//   double, rounded once, written by thread 0 of the row's workgroup: no launch and no workspace more.
 #include "pdr_common.h"
 
 namespace {
@@ -84,6 +97,27 @@ __device__ __forceinline__ void block_sum2(double& a, double& b) {
   __syncthreads();
   a = ((lds[0] + lds[2]) + lds[4]) + lds[6];
   b = ((lds[1] + lds[3]) + lds[5]) + lds[7];
+}
+
+// the same for three sums (the row kernel with grad_e): the order of each is block_sum2's
+__device__ __forceinline__ void block_sum3(double& a, double& b, double& c) {
+  __shared__ double lds[12];
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) {
+    a += __shfl_xor(a, off, 64);
+    b += __shfl_xor(b, off, 64);
+    c += __shfl_xor(c, off, 64);
+  }
+  const int w = threadIdx.x >> 6;
+  if (pdr::lane_id() == 0) {
+    lds[3 * w] = a;
+    lds[3 * w + 1] = b;
+    lds[3 * w + 2] = c;
+  }
+  __syncthreads();
+  a = ((lds[0] + lds[3]) + lds[6]) + lds[9];
+  b = ((lds[1] + lds[4]) + lds[7]) + lds[10];
+  c = ((lds[2] + lds[5]) + lds[8]) + lds[11];
 }
 
 template <int V>
@@ -173,11 +207,13 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const float* __restrict__
   }
 }
 
-template <int V, int ACT>
+// ADD: y = fl(fl(act(z) + e[row]) + res[row, s]), e / res each may be NULL (not both: the host launches ADD = false)
+template <int V, int ACT, bool ADD>
 __global__ __launch_bounds__(256) void gn_apply_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
                                                        const float* __restrict__ beta,
                                                        const double* __restrict__ part, int C, long S, int G, int Cg,
-                                                       int Cn, int P, float eps, float* __restrict__ y,
+                                                       int Cn, int P, float eps, const float* __restrict__ e,
+                                                       const float* __restrict__ res, float* __restrict__ y,
                                                        float* __restrict__ mean_out, float* __restrict__ rstd_out) {
   const size_t row = blockIdx.x;                       // b C + c
   const size_t b = row / C;
@@ -209,6 +245,26 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const float* __restrict__
   const float* xr = x + row * static_cast<size_t>(S);
   float* yr = y + row * static_cast<size_t>(S);
   const long step = static_cast<long>(gridDim.y) * 256 * V;
+  if (ADD) {
+    const bool has_e = e != nullptr;                   // uniform over the grid
+    const float ev = has_e ? e[row] : 0.0f;            // one value per workgroup
+    const float* rr = res ? res + row * static_cast<size_t>(S) : nullptr;
+    for (long i = (static_cast<long>(blockIdx.y) * 256 + threadIdx.x) * V; i < S; i += step) {
+      Pack<V> p, q;
+      p.load(xr + i);
+      if (rr) q.load(rr + i);
+#pragma unroll
+      for (int j = 0; j < V; ++j) {
+        float xh;
+        float a = act_of<ACT>(z_of(r, p.v[j], &xh));
+        if (has_e) a = a + ev;
+        if (rr) a = a + q.v[j];
+        p.v[j] = a;
+      }
+      p.store(yr + i);
+    }
+    return;
+  }
   for (long i = (static_cast<long>(blockIdx.y) * 256 + threadIdx.x) * V; i < S; i += step) {
     Pack<V> p;
     p.load(xr + i);
@@ -237,19 +293,35 @@ __device__ __forceinline__ Row row_of(const float* __restrict__ gamma, const flo
   return r;
 }
 
-template <int V, int ACT>
+// GE: also ge[row] = float(sum_s double(dy)), the raw dy in the order of r2, on EVERY row (pass-through rows read dy
+// alone and write no row sums)
+template <int V, int ACT, bool GE>
 __global__ __launch_bounds__(256) void gn_rows_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
                                                       const float* __restrict__ beta, const float* __restrict__ mean,
                                                       const float* __restrict__ rstd, const float* __restrict__ dy,
                                                       int C, long S, int G, int Cg, int Cn,
-                                                      double* __restrict__ rows) {
+                                                      double* __restrict__ rows, float* __restrict__ ge) {
   const size_t row = blockIdx.x;
   const int c = static_cast<int>(row % C);
-  if (c >= Cn) return;                                 // the whole workgroup: a pass-through row has no sums
+  const float* gr = dy + row * static_cast<size_t>(S);
+  if (c >= Cn) {                                       // the whole workgroup: a pass-through row has no row sums
+    if (GE) {
+      double r3 = 0.0, none = 0.0;
+#pragma unroll 2
+      for (long i = static_cast<long>(threadIdx.x) * V; i < S; i += 256 * V) {
+        Pack<V> q;
+        q.load(gr + i);
+#pragma unroll
+        for (int j = 0; j < V; ++j) r3 += static_cast<double>(q.v[j]);
+      }
+      block_sum2(r3, none);
+      if (threadIdx.x == 0) ge[row] = static_cast<float>(r3);
+    }
+    return;
+  }
   const Row r = row_of(gamma, beta, mean, rstd, row / C, c, G, Cg, Cn);
   const float* xr = x + row * static_cast<size_t>(S);
-  const float* gr = dy + row * static_cast<size_t>(S);
-  double r1 = 0.0, r2 = 0.0;
+  double r1 = 0.0, r2 = 0.0, r3 = 0.0;
 #pragma unroll 2
   for (long i = static_cast<long>(threadIdx.x) * V; i < S; i += 256 * V) {
     Pack<V> p, q;
@@ -262,12 +334,17 @@ __global__ __launch_bounds__(256) void gn_rows_kernel(const float* __restrict__ 
       const double dz = static_cast<double>(dz_of<ACT>(z, q.v[j]));
       r1 = __builtin_fma(dz, static_cast<double>(xh), r1);
       r2 += dz;
+      if (GE) r3 += static_cast<double>(q.v[j]);
     }
   }
-  block_sum2(r1, r2);
+  if (GE)
+    block_sum3(r1, r2, r3);
+  else
+    block_sum2(r1, r2);
   if (threadIdx.x == 0) {
     rows[row * 2] = r1;
     rows[row * 2 + 1] = r2;
+    if (GE) ge[row] = static_cast<float>(r3);
   }
 }
 
@@ -363,6 +440,81 @@ unsigned chunks_of(long S) {
     PDR_GN_BY_ACT(1, CALL);     \
   }
 
+// both forward entries: add == residual == NULL launches the kernels pdr_group_norm_act always launched
+int forward(const float* x, const float* gamma, const float* beta, const float* add, const float* residual, int B,
+            int C, long S, int G, float eps, int act, float* y, float* mean, float* rstd, void* workspace,
+            pdr_stream_t stream) {
+  long long n;
+  const int rc = check_sizes(B, C, S, G, act, eps, &n);
+  if (rc != PDR_OK || n == 0) return rc;
+  if (!x || !y || !workspace || (gamma == nullptr) != (beta == nullptr)) return PDR_EINVAL;
+  const Plan p = plan_of(C, S, G, aligned16(x) && aligned16(y) && aligned16(residual));
+  const int Cn = p.Cg * G, P = static_cast<int>(p.P);
+  const long m = p.Cg * S;
+  double* part = static_cast<double*>(workspace);
+  hipStream_t st = pdr::as_stream(stream);
+  const dim3 gs(static_cast<unsigned>(B) * G, static_cast<unsigned>(P)), ga(static_cast<unsigned>(B) * C, chunks_of(S));
+  if (p.vec)
+    hipLaunchKernelGGL(gn_stats_kernel<4>, gs, dim3(256), 0, st, x, C, S, G, p.Cg, m, p.E, part);
+  else
+    hipLaunchKernelGGL(gn_stats_kernel<1>, gs, dim3(256), 0, st, x, C, S, G, p.Cg, m, p.E, part);
+#define PDR_GN_APPLY(V, A)                                                                                         \
+  hipLaunchKernelGGL((gn_apply_kernel<V, A, false>), ga, dim3(256), 0, st, x, gamma, beta, part, C, S, G, p.Cg, Cn, P, \
+                     eps, add, residual, y, mean, rstd)
+#define PDR_GN_APPLY_ADD(V, A)                                                                                    \
+  hipLaunchKernelGGL((gn_apply_kernel<V, A, true>), ga, dim3(256), 0, st, x, gamma, beta, part, C, S, G, p.Cg, Cn, P, \
+                     eps, add, residual, y, mean, rstd)
+  if (add || residual) {
+    PDR_GN_BY_FAMILY(PDR_GN_APPLY_ADD)
+  } else {
+    PDR_GN_BY_FAMILY(PDR_GN_APPLY)
+  }
+#undef PDR_GN_APPLY
+#undef PDR_GN_APPLY_ADD
+  return pdr::check_launch();
+}
+
+// both backward entries: grad_add == NULL launches the kernels pdr_group_norm_act_grad always launched
+int backward(const float* x, const float* gamma, const float* beta, const float* mean, const float* rstd,
+             const float* grad_y, int B, int C, long S, int G, int act, float* grad_x, float* grad_gamma,
+             float* grad_beta, float* grad_add, void* workspace, pdr_stream_t stream) {
+  long long n;
+  const int rc = check_sizes(B, C, S, G, act, 0.0f, &n);
+  if (rc != PDR_OK || n == 0) return rc;
+  if (!x || !mean || !rstd || !grad_y || !workspace || (gamma == nullptr) != (beta == nullptr)) return PDR_EINVAL;
+  if (!gamma && (grad_gamma || grad_beta)) return PDR_EINVAL;
+  if (!grad_x && !grad_gamma && !grad_beta && !grad_add) return PDR_EINVAL;
+  const Plan p = plan_of(C, S, G, aligned16(x) && aligned16(grad_y) && aligned16(grad_x));
+  const int Cn = p.Cg * G;
+  double* rows = static_cast<double*>(workspace);
+  hipStream_t st = pdr::as_stream(stream);
+  const dim3 gr(static_cast<unsigned>(B) * C), ga(static_cast<unsigned>(B) * C, chunks_of(S));
+#define PDR_GN_ROWS(V, A)                                                                                          \
+  hipLaunchKernelGGL((gn_rows_kernel<V, A, false>), gr, dim3(256), 0, st, x, gamma, beta, mean, rstd, grad_y, C, S, G, \
+                     p.Cg, Cn, rows, grad_add)
+#define PDR_GN_ROWS_GE(V, A)                                                                                      \
+  hipLaunchKernelGGL((gn_rows_kernel<V, A, true>), gr, dim3(256), 0, st, x, gamma, beta, mean, rstd, grad_y, C, S, G, \
+                     p.Cg, Cn, rows, grad_add)
+  if (grad_add) {
+    PDR_GN_BY_FAMILY(PDR_GN_ROWS_GE)
+  } else {
+    PDR_GN_BY_FAMILY(PDR_GN_ROWS)
+  }
+#undef PDR_GN_ROWS
+#undef PDR_GN_ROWS_GE
+  if (grad_x) {
+#define PDR_GN_DX(V, A)                                                                                              \
+  hipLaunchKernelGGL((gn_dx_kernel<V, A>), ga, dim3(256), 0, st, x, gamma, beta, mean, rstd, grad_y, rows, C, S, G, \
+                     p.Cg, Cn, grad_x)
+    PDR_GN_BY_FAMILY(PDR_GN_DX)
+#undef PDR_GN_DX
+  }
+  if (grad_gamma || grad_beta)
+    hipLaunchKernelGGL(gn_dparam_kernel, dim3((Cn + 255) / 256), dim3(256), 0, st, rows, B, C, Cn, grad_gamma,
+                       grad_beta);
+  return pdr::check_launch();
+}
+
 }  // namespace
 
 extern "C" size_t pdr_group_norm_act_workspace_bytes(int B, int C, long S, int G) {
@@ -386,57 +538,27 @@ extern "C" int pdr_group_norm_act_plan(int C, long S, int G, int aligned16, long
 extern "C" int pdr_group_norm_act(const float* x, const float* gamma, const float* beta, int B, int C, long S, int G,
                                   float eps, int act, float* y, float* mean, float* rstd, void* workspace,
                                   pdr_stream_t stream) {
-  long long n;
-  const int rc = check_sizes(B, C, S, G, act, eps, &n);
-  if (rc != PDR_OK || n == 0) return rc;
-  if (!x || !y || !workspace || (gamma == nullptr) != (beta == nullptr)) return PDR_EINVAL;
-  const Plan p = plan_of(C, S, G, aligned16(x) && aligned16(y));
-  const int Cn = p.Cg * G, P = static_cast<int>(p.P);
-  const long m = p.Cg * S;
-  double* part = static_cast<double*>(workspace);
-  hipStream_t st = pdr::as_stream(stream);
-  const dim3 gs(static_cast<unsigned>(B) * G, static_cast<unsigned>(P)), ga(static_cast<unsigned>(B) * C, chunks_of(S));
-  if (p.vec)
-    hipLaunchKernelGGL(gn_stats_kernel<4>, gs, dim3(256), 0, st, x, C, S, G, p.Cg, m, p.E, part);
-  else
-    hipLaunchKernelGGL(gn_stats_kernel<1>, gs, dim3(256), 0, st, x, C, S, G, p.Cg, m, p.E, part);
-#define PDR_GN_APPLY(V, A)                                                                                         \
-  hipLaunchKernelGGL((gn_apply_kernel<V, A>), ga, dim3(256), 0, st, x, gamma, beta, part, C, S, G, p.Cg, Cn, P, eps, y, \
-                     mean, rstd)
-  PDR_GN_BY_FAMILY(PDR_GN_APPLY)
-#undef PDR_GN_APPLY
-  return pdr::check_launch();
+  return forward(x, gamma, beta, nullptr, nullptr, B, C, S, G, eps, act, y, mean, rstd, workspace, stream);
+}
+
+extern "C" int pdr_group_norm_act_add(const float* x, const float* gamma, const float* beta, const float* add,
+                                      const float* residual, int B, int C, long S, int G, float eps, int act, float* y,
+                                      float* mean, float* rstd, void* workspace, pdr_stream_t stream) {
+  return forward(x, gamma, beta, add, residual, B, C, S, G, eps, act, y, mean, rstd, workspace, stream);
 }
 
 extern "C" int pdr_group_norm_act_grad(const float* x, const float* gamma, const float* beta, const float* mean,
                                        const float* rstd, const float* grad_y, int B, int C, long S, int G, int act,
                                        float* grad_x, float* grad_gamma, float* grad_beta, void* workspace,
                                        pdr_stream_t stream) {
-  long long n;
-  const int rc = check_sizes(B, C, S, G, act, 0.0f, &n);
-  if (rc != PDR_OK || n == 0) return rc;
-  if (!x || !mean || !rstd || !grad_y || !workspace || (gamma == nullptr) != (beta == nullptr)) return PDR_EINVAL;
-  if (!gamma && (grad_gamma || grad_beta)) return PDR_EINVAL;
-  if (!grad_x && !grad_gamma && !grad_beta) return PDR_EINVAL;
-  const Plan p = plan_of(C, S, G, aligned16(x) && aligned16(grad_y) && aligned16(grad_x));
-  const int Cn = p.Cg * G;
-  double* rows = static_cast<double*>(workspace);
-  hipStream_t st = pdr::as_stream(stream);
-  const dim3 gr(static_cast<unsigned>(B) * C), ga(static_cast<unsigned>(B) * C, chunks_of(S));
-#define PDR_GN_ROWS(V, A)                                                                                          \
-  hipLaunchKernelGGL((gn_rows_kernel<V, A>), gr, dim3(256), 0, st, x, gamma, beta, mean, rstd, grad_y, C, S, G, p.Cg, \
-                     Cn, rows)
-  PDR_GN_BY_FAMILY(PDR_GN_ROWS)
-#undef PDR_GN_ROWS
-  if (grad_x) {
-#define PDR_GN_DX(V, A)                                                                                              \
-  hipLaunchKernelGGL((gn_dx_kernel<V, A>), ga, dim3(256), 0, st, x, gamma, beta, mean, rstd, grad_y, rows, C, S, G, \
-                     p.Cg, Cn, grad_x)
-    PDR_GN_BY_FAMILY(PDR_GN_DX)
-#undef PDR_GN_DX
-  }
-  if (grad_gamma || grad_beta)
-    hipLaunchKernelGGL(gn_dparam_kernel, dim3((Cn + 255) / 256), dim3(256), 0, st, rows, B, C, Cn, grad_gamma,
-                       grad_beta);
-  return pdr::check_launch();
+  return backward(x, gamma, beta, mean, rstd, grad_y, B, C, S, G, act, grad_x, grad_gamma, grad_beta, nullptr,
+                  workspace, stream);
+}
+
+extern "C" int pdr_group_norm_act_add_grad(const float* x, const float* gamma, const float* beta, const float* mean,
+                                           const float* rstd, const float* grad_y, int B, int C, long S, int G,
+                                           int act, float* grad_x, float* grad_gamma, float* grad_beta,
+                                           float* grad_add, void* workspace, pdr_stream_t stream) {
+  return backward(x, gamma, beta, mean, rstd, grad_y, B, C, S, G, act, grad_x, grad_gamma, grad_beta, grad_add,
+                  workspace, stream);
 }

@@ -13,8 +13,13 @@ neighbour search to the one op `pointnet2_utils.knn_and_group` instead of knn_ga
 and two transposes.
 `set_fused_score_norm(True | False)` (default False) makes `AttentionModule` run the front of its score head -- expand,
 cat, then each [ReLU, MyGroupNorm] pair of `weight_conv` -- as the one op `pointnet2_utils.relu_group_norm`, which
-never builds the cat."""
+never builds the cat.
+`set_fused_injection(True | False)` (default False) makes `Mlp_plus_t_emb` fold the embedding it adds behind each of its
+[conv, MyGroupNorm, act] stacks, and the residual behind the last one, into the stack's last norm and activation: the
+one op `pointnet2_utils.group_norm_act_add` instead of the norm, the activation, the broadcast adds and the residual
+add."""
 from . import pointnet2_modules, pointnet2_utils  # noqa: F401
 from ._ext import (is_deterministic, is_fused_attention_pool, is_fused_group_norm, is_fused_grouping,  # noqa: F401
-                   is_fused_knn_grouping, is_fused_score_norm, set_deterministic, set_fused_attention_pool,
-                   set_fused_group_norm, set_fused_grouping, set_fused_knn_grouping, set_fused_score_norm)
+                   is_fused_injection, is_fused_knn_grouping, is_fused_score_norm, set_deterministic,
+                   set_fused_attention_pool, set_fused_group_norm, set_fused_grouping, set_fused_injection,
+                   set_fused_knn_grouping, set_fused_score_norm)

@@ -163,6 +163,27 @@ def is_fused_score_norm():
     return _fused_score_norm
 
 
+_fused_injection = False          # set_fused_injection: Mlp_plus_t_emb's adds run inside pdr_group_norm_act_add
+
+
+def set_fused_injection(mode):
+    """Process-wide switch: True = `Mlp_plus_t_emb.forward` hands the last [MyGroupNorm, ReLU / Swish] of each of its
+    stacks, together with the embedding it injects behind that stack and (behind the last stack) the residual, to the
+    one op `pointnet2_utils.group_norm_act_add` for fp32 GPU tensors of a shape the kernels support; False
+    (the default) = the stack followed by the broadcast adds and the residual add, as ever.  Independent of the other
+    switches.  Returns the previous setting."""
+    global _fused_injection
+    if not isinstance(mode, bool):
+        raise TypeError("set_fused_injection takes True or False, got %r" % (mode,))
+    prev, _fused_injection = _fused_injection, mode
+    return prev
+
+
+def is_fused_injection():
+    """Whether Mlp_plus_t_emb folds its injections and residual into the GroupNorm + activation op right now."""
+    return _fused_injection
+
+
 def _scatter_workspace(B, P, N, device):
     """Scratch of one `*_grad_det` call (pdr_scatter_workspace_bytes), a torch allocation per call."""
     nbytes = _lib.load().pdr_scatter_workspace_bytes(int(B), int(P), int(N))
@@ -670,6 +691,68 @@ def group_norm_act_grad(x, weight, bias, mean, rstd, grad_y, num_groups, act="no
                                                        _ptr(gw), _ptr(gb), ws.data_ptr(), _stream()),
                    "group_norm_act_grad")
     return gx, gw, gb
+
+
+def _req_injection(x, B, C, add, residual):
+    """Shapes and dtypes of group_norm_act_add's optional terms: add (B, C), residual of x's shape."""
+    if add is not None:
+        _req(add, "add", torch.float32)
+        _same_device(x, add)
+        if tuple(add.shape) != (B, C):
+            raise RuntimeError("add must have shape (B, C) = (%d, %d), got %s" % (B, C, tuple(add.shape)))
+    if residual is not None:
+        _req(residual, "residual", torch.float32)
+        _same_device(x, residual)
+        if residual.shape != x.shape:
+            raise RuntimeError("residual must have x's shape %s, got %s" % (tuple(x.shape), tuple(residual.shape)))
+
+
+def group_norm_act_add(x, weight, bias, num_groups, eps=1e-5, act="none", add=None, residual=None):
+    """(act(MyGroupNorm(x)) + add[:, :, None]) + residual in the two launches of group_norm_act
+    (pdr_group_norm_act_add): x, weight, bias as there, add (B, C) f32 or None, residual like x or None ->
+    (y like x, mean (B, G), rstd (B, G)).  mean and rstd have group_norm_act's bits, y those of its y followed by the
+    two fp32 additions in that order; a term that is None is skipped."""
+    B, C, S, G, code = _req_group_norm(x, weight, bias, num_groups, act)
+    _req_injection(x, B, C, add, residual)
+    y = torch.empty_like(x)
+    mean = torch.empty((B, max(G, 0)), dtype=torch.float32, device=x.device)
+    rstd = torch.empty_like(mean)
+    ws = _group_norm_workspace(B, C, S, G, x.device)
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.load().pdr_group_norm_act_add(x.data_ptr(), _ptr(weight), _ptr(bias), _ptr(add), _ptr(residual),
+                                                      B, C, S, G, float(eps), code, y.data_ptr(), mean.data_ptr(),
+                                                      rstd.data_ptr(), ws.data_ptr(), _stream()), "group_norm_act_add")
+    return y, mean, rstd
+
+
+def group_norm_act_add_grad(x, weight, bias, mean, rstd, grad_y, num_groups, act="none", need_x=True, need_weight=True,
+                            need_bias=True, need_add=True):
+    """Backward of group_norm_act_add in the three launches of group_norm_act_grad (pdr_group_norm_act_add_grad); it
+    needs neither add nor residual.  -> (grad_x, grad_weight, grad_bias, grad_add (B, C)), None where not needed (at
+    least one must be).  The first three have group_norm_act_grad's bits; grad_add is the row sum of grad_y, in double
+    in the row kernel's order, rounded once.  The residual's gradient is grad_y itself."""
+    B, C, S, G, code = _req_group_norm(x, weight, bias, num_groups, act)
+    _req(grad_y, "grad_y", torch.float32)
+    if grad_y.shape != x.shape:
+        raise RuntimeError("grad_y must have x's shape %s, got %s" % (tuple(x.shape), tuple(grad_y.shape)))
+    for t, name in ((mean, "mean"), (rstd, "rstd")):
+        _req(t, name, torch.float32)
+        if tuple(t.shape) != (B, G):
+            raise RuntimeError("%s must have shape (B, G) = (%d, %d), got %s" % (name, B, G, tuple(t.shape)))
+    _same_device(x, grad_y, mean, rstd)
+    gx = torch.empty_like(x) if need_x else None
+    gw = torch.empty_like(weight) if need_weight and weight is not None else None
+    gb = torch.empty_like(bias) if need_bias and bias is not None else None
+    ge = torch.empty((B, C), dtype=torch.float32, device=x.device) if need_add else None
+    if B * C * S == 0 and ge is not None:                    # the empty problem launches nothing: a sum of nothing
+        ge.zero_()
+    ws = _group_norm_workspace(B, C, S, G, x.device)
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.load().pdr_group_norm_act_add_grad(x.data_ptr(), _ptr(weight), _ptr(bias), mean.data_ptr(),
+                                                           rstd.data_ptr(), grad_y.data_ptr(), B, C, S, G, code,
+                                                           _ptr(gx), _ptr(gw), _ptr(gb), _ptr(ge), ws.data_ptr(),
+                                                           _stream()), "group_norm_act_add_grad")
+    return gx, gw, gb, ge
 
 
 def _req_relu_group_norm(q, k, weight, bias, num_groups):

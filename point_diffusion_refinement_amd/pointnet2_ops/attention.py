@@ -12,7 +12,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _ext
-from .pointnet2_utils import attention_pool, group_norm_act, relu_group_norm
+from .pointnet2_utils import attention_pool, group_norm_act, group_norm_act_add, relu_group_norm
 
 
 class MyGroupNorm(nn.Module):
@@ -40,6 +40,17 @@ class MyGroupNorm(nn.Module):
             x.shape[1] - x.shape[1] % self.num_groups == self.num_channels and \
             _ext.group_norm_act_supported(x.shape, self.num_groups)
 
+    def injectable(self, x, add, residual):
+        """x, add (B, C) and residual (x's shape), the last two optional, are fp32 GPU tensors of a shape
+        pdr_group_norm_act_add takes.  Reached only under `set_fused_injection(True)`; independent of
+        `set_fused_group_norm`.  Like `fusable` it does not ask for dense strides: `group_norm_act_add` copies a tensor
+        that is not contiguous (the transposed groups of an unfused group_knn are the one such case in the network)."""
+        C = x.shape[1]
+        for t, shape in ((x, x.shape), (add, (x.shape[0], C)), (residual, x.shape)):
+            if t is not None and not (t.is_cuda and t.dtype == torch.float32 and t.shape == shape):
+                return False
+        return C - C % self.num_groups == self.num_channels and _ext.group_norm_act_supported(x.shape, self.num_groups)
+
     def fused(self, x, act):
         """act(self(x)) as one op: two launches forward, three backward, only x and (B, G) statistics saved."""
         gn = self.group_norm
@@ -61,7 +72,11 @@ class NormActSequential(nn.Sequential):
     def forward(self, x):
         if not _ext.is_fused_group_norm():
             return super().forward(x)
-        mods = list(self)
+        return self._run(list(self), x)
+
+    @staticmethod
+    def _run(mods, x):
+        """The modules `mods` in order, a fusable MyGroupNorm and the activation after it as one op."""
         i = 0
         while i < len(mods):
             m = mods[i]
@@ -73,6 +88,31 @@ class NormActSequential(nn.Sequential):
                 x = m(x)
                 i += 1
         return x
+
+    def forward_add(self, x, add=None, residual=None):
+        """(self(x) + add[:, :, None, ..]) + residual, add (B, C) and residual (self(x)'s shape) each optional: what
+        Mlp_plus_t_emb computes behind a stack (`set_fused_injection`).  Where the stack ends in a MyGroupNorm and an
+        activation `group_norm_act` can absorb, and the norm's input, add and residual are fp32 GPU tensors of a
+        shape the kernels take, the children before that pair run as `forward` runs them and the pair and the adds
+        are ONE `group_norm_act_add` op; otherwise `forward` and the two torch additions."""
+        if add is None and residual is None:
+            return self.forward(x)
+        mods = list(self)
+        n = len(mods) - 2
+        if n >= 0 and isinstance(mods[n], MyGroupNorm) and fused_act_of(mods[n + 1]):
+            h = self._run(mods[:n], x)                     # (fusable is False with set_fused_group_norm off)
+            if mods[n].injectable(h, add, residual):
+                gn = mods[n].group_norm
+                return group_norm_act_add(h, gn.weight, gn.bias, mods[n].num_groups, gn.eps, fused_act_of(mods[n + 1]),
+                                          add, residual)
+            h = self._run(mods[n:], h)
+        else:
+            h = self.forward(x)
+        if add is not None:
+            h = h + add[(slice(None), slice(None)) + (None,) * (h.dim() - 2)]
+        if residual is not None:
+            h = h + residual
+        return h
 
 
 def count_to_mask(count, K):

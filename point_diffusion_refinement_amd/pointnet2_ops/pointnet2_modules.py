@@ -13,7 +13,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import pointnet2_utils
+from . import _ext, pointnet2_utils
 from .attention import AttentionModule, MyGroupNorm, NormActSequential
 
 
@@ -96,9 +96,38 @@ class Mlp_plus_t_emb(nn.Module):
     def _inject(h, fc, emb):
         return h + fc(emb).unsqueeze(2).unsqueeze(3)
 
+    def _forward_injected(self, feature, t_emb, condition_emb, second_condition_emb):
+        """forward under `set_fused_injection(True)`: every embedding, and the residual, goes into the
+        `forward_add` of the stack it follows -- one `group_norm_act_add` op per stack where that applies -- instead
+        of a broadcast add of its own.  The same checks, the same order of additions."""
+        def embedding(include, fc, emb, name, refusal):
+            if not include:
+                if emb is not None:
+                    raise Exception('This module does not include %s but %s is given' % refusal)
+                return None
+            if emb is None:
+                raise Exception('Should pass %s to the forward function' % name)
+            return getattr(self, fc)(emb)
+
+        e_t = embedding(self.include_t, 'fc', t_emb, 't_emb', ('t', 't_emb'))
+        e_c = embedding(self.include_condition, 'fc_condition', condition_emb, 'condition_emb',
+                        ('condition', 'condition_emb'))
+        e_c2 = embedding(self.include_second_condition, 'fc_second_condition', second_condition_emb,
+                         'second_condition_emb', ('condition', 'condition_emb'))
+        res = None
+        if self.res_connect_bool:
+            res = feature if self.res_connect is None else self.res_connect(feature)
+        h = self.first_mlp.forward_add(feature, add=e_t)
+        if self.rest_mlp is None:                         # (no second condition without a rest_mlp: __init__ asserts it)
+            return self.second_mlp.forward_add(h, add=e_c, residual=res)
+        h = self.second_mlp.forward_add(h, add=e_c)
+        return self.rest_mlp.forward_add(h, add=e_c2, residual=res)
+
     def forward(self, feature, t_emb=None, condition_emb=None, second_condition_emb=None):
         if self.first_conv_bool:
             feature = self.first_conv(feature)
+        if _ext._fused_injection:                         # read directly: with the switch off this path calls nothing
+            return self._forward_injected(feature, t_emb, condition_emb, second_condition_emb)
         h = self.first_mlp(feature)
         if self.include_t:
             if t_emb is None:

@@ -202,6 +202,45 @@ def group_norm_act(x, weight, bias, num_groups, eps=1e-5, act='none'):
     return GroupNormAct.apply(x.contiguous(), weight, bias, num_groups, eps, act)
 
 
+class GroupNormActAdd(Function):
+    """(act(MyGroupNorm(x)) + add[:, :, None]) + residual: _ext.group_norm_act_add.  Saves what GroupNormAct saves --
+    x, weight, bias and the (B, G) mean / rstd -- and nothing of the output's size: the backward needs neither add nor
+    residual.  The residual's gradient is grad_y itself; add's is its row sum, from the row kernel of the backward."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, add, residual, num_groups, eps, act):
+        y, mean, rstd = _ext.group_norm_act_add(x, weight, bias, num_groups, eps, act, add, residual)
+        ctx.num_groups, ctx.act, ctx.affine = num_groups, act, weight is not None
+        if ctx.affine:
+            ctx.save_for_backward(x, mean, rstd, weight, bias)
+        else:
+            ctx.save_for_backward(x, mean, rstd)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_y):
+        x, mean, rstd = ctx.saved_tensors[:3]
+        weight, bias = ctx.saved_tensors[3:] if ctx.affine else (None, None)
+        need_x, need_e, need_r = ctx.needs_input_grad[0], ctx.needs_input_grad[3], ctx.needs_input_grad[4]
+        need_w, need_b = (ctx.needs_input_grad[1], ctx.needs_input_grad[2]) if ctx.affine else (False, False)
+        grad_y = grad_y.contiguous().float()
+        gx = gw = gb = ge = None
+        if need_x or need_w or need_b or need_e:
+            gx, gw, gb, ge = _ext.group_norm_act_add_grad(x, weight, bias, mean, rstd, grad_y, ctx.num_groups, ctx.act,
+                                                          need_x, need_w, need_b, need_e)
+        return gx, gw, gb, ge, (grad_y if need_r else None), None, None, None
+
+
+def group_norm_act_add(x, weight, bias, num_groups, eps=1e-5, act='none', add=None, residual=None):
+    """group_norm_act with the two adds Mlp_plus_t_emb makes behind a stack folded in, as one differentiable op
+    (pdr_group_norm_act_add / pdr_group_norm_act_add_grad): add (B, C) or None is broadcast over the trailing
+    dimensions, residual (x's shape) or None is added after it -- (act(MyGroupNorm(x)) + add[:, :, None]) + residual,
+    the composition's order and roundings."""
+    return GroupNormActAdd.apply(x.contiguous(), weight, bias, None if add is None else add.contiguous(),
+                                 None if residual is None else residual.contiguous(), num_groups, eps, act)
+
+
 class ReluGroupNorm(Function):
     """MyGroupNorm(relu([q over K | k])): _ext.relu_group_norm.  Saves q, k, weight, bias and the (B, G) mean / rstd --
     neither the cat nor y; the backward recomputes the normalised values from them and is order-fixed."""

@@ -1,14 +1,17 @@
 """Forward plus backward of the whole DDPM network on the module (trainable) path with an MSE loss on its output: all
 five one-op switches off (set_fused_attention_pool, set_fused_group_norm, set_fused_grouping, set_fused_knn_grouping,
-set_fused_score_norm) against all five on.  DESIGN sections 7a.3 to 7a.7 each list this figure as not measured.
+set_fused_score_norm) against all five on, and against all five and set_fused_injection on (the setting "six", DESIGN
+7a.9).  DESIGN sections 7a.3 to 7a.7 each list this figure as not measured.
 
-One child process per setting, each under its own time limit; the first child that fails ends the run.  In a child:
+One child process per setting and round (--rounds > 1 alternates the settings: off, on, six, off, on, six, ..), each
+under its own time limit; the first child that fails ends the run.  In a child:
 PointNet2CloudCondition(ddpm_pointnet_config()) with seed 0, configs.synthetic_batch(B), a fixed random target; device
 events around one forward + loss + backward (gradients cleared before, no optimiser step), warm-up steps, then
 repetitions, the median; torch.cuda.max_memory_allocated over the timed steps.  Running out of device memory is a
 RESULT ({"oom": true}), not an error.
 
-    python tools/train_step_bench.py [--B 8] [--reps 10] [--warmup 3] [--limit 300] [--out profiles/train_step.json]
+    python tools/train_step_bench.py [--B 8] [--reps 10] [--warmup 3] [--limit 300] [--settings off,on,six] [--rounds 1]
+                                     [--out profiles/train_step_injection.json]
 """
 import argparse
 import json
@@ -23,9 +26,10 @@ if ROOT not in sys.path:
 
 SWITCHES = ("set_fused_attention_pool", "set_fused_group_norm", "set_fused_grouping", "set_fused_knn_grouping",
             "set_fused_score_norm")
+SETTINGS = {"off": (), "on": SWITCHES, "six": SWITCHES + ("set_fused_injection",)}
 
 
-def measure(on, B, reps, warmup):
+def measure(setting, B, reps, warmup):
     import torch
     from point_diffusion_refinement_amd import pointnet2_ops
     from point_diffusion_refinement_amd.pointnet2 import configs
@@ -33,13 +37,14 @@ def measure(on, B, reps, warmup):
     if not torch.cuda.is_available():
         sys.exit("train_step_bench: no GPU (the module path has no CPU ops)")
     dev = torch.device("cuda:0")
-    for name in SWITCHES:
-        getattr(pointnet2_ops, name)(on)
+    on = SETTINGS[setting]
+    for name in SETTINGS["six"]:
+        getattr(pointnet2_ops, name)(name in on)
     torch.manual_seed(0)
     net = PointNet2CloudCondition(configs.ddpm_pointnet_config()).to(dev).train()
     x, cond, label = configs.synthetic_batch(B, device=dev)
     ts = torch.full((B,), 500.0, device=dev)
-    row = {"switches_on": on, "B": B, "oom": False}
+    row = {"setting": setting, "switches_on": [n[len("set_fused_"):] for n in on], "B": B, "oom": False}
 
     def step():
         net.zero_grad(set_to_none=True)
@@ -91,18 +96,26 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--limit", type=int, default=300, help="time limit of one child process, seconds")
     ap.add_argument("--out", default="")
-    ap.add_argument("--one", default="", help="(child) measure one setting: on | off")
+    ap.add_argument("--settings", default="off,on,six", help="comma-separated: off | on (five switches) | six")
+    ap.add_argument("--rounds", type=int, default=1, help="processes per setting, the settings alternating")
+    ap.add_argument("--one", default="", help="(child) measure one setting: off | on | six")
     args = ap.parse_args()
     if args.one:
-        print(json.dumps(measure(args.one == "on", args.B, args.reps, args.warmup)), flush=True)
+        print(json.dumps(measure(args.one, args.B, args.reps, args.warmup)), flush=True)
         return
-    result = {"tool": "train_step_bench", "B": args.B, "reps": args.reps, "warmup": args.warmup, "rows": []}
-    for setting in ("off", "on"):
-        row = child(["--one", setting, "--B", str(args.B), "--reps", str(args.reps), "--warmup", str(args.warmup)],
-                    args.limit, "switches " + setting)
-        result["rows"].append(row)
-        sys.stderr.write("switches %-3s  %s\n" % (setting, "out of memory" if row["oom"] else
-                                                  "%.1f ms  peak %.0f MiB" % (row["step_ms"], row["peak_bytes"] / 2 ** 20)))
+    settings = args.settings.split(",")
+    if not settings or any(s not in SETTINGS for s in settings):
+        ap.error("--settings takes a comma-separated list of %s" % ", ".join(SETTINGS))
+    result = {"tool": "train_step_bench", "B": args.B, "reps": args.reps, "warmup": args.warmup,
+              "rounds": args.rounds, "rows": []}
+    for rnd in range(args.rounds):
+        for setting in settings:
+            row = child(["--one", setting, "--B", str(args.B), "--reps", str(args.reps), "--warmup", str(args.warmup)],
+                        args.limit, "switches " + setting)
+            row["round"] = rnd
+            result["rows"].append(row)
+            sys.stderr.write("round %d switches %-3s  %s\n" % (rnd, setting, "out of memory" if row["oom"] else
+                             "%.1f ms  peak %.0f MiB" % (row["step_ms"], row["peak_bytes"] / 2 ** 20)))
     line = json.dumps(result)
     print(line, flush=True)
     if args.out:
