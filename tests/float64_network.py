@@ -21,6 +21,10 @@ decision are left once the geometry is shared, and a gradient is only comparable
     relu_tape("record")        the ReLU masks of a forward, one per site in call order -- the fused entries that hold a
     relu_tape("replay", tape)  ReLU record the same sites as the composition -- and their replay in another
                                evaluation (the float64 model under the masks of the fp32 run it is the reference of)
+    chamfer_tape("record", nn=..)   the nearest-neighbour assignment of every Chamfer term of a loss (the stage-two
+    chamfer_tape("replay", tape)    step: it depends on the network's output) and its replay by gathers in float64;
+                               chamfer_tape_honesty: a taped index differs from float64's own argmin only where the
+                               output error can move the two distances past each other
     record_max_gaps(net)       the two max-over-points of the global PointNet are NOT pinned; this measures how far
                                each of them is from a tie, so a test can assert that no evaluation can pick another point
     coordinate_leaf(net, x)    a leaf in place of the level-0 coordinates (forward() cuts the graph at its input)
@@ -330,6 +334,132 @@ def relu_tape(mode, tape=None):
     finally:
         torch.nn.ReLU.forward = relu_forward
         _ext.group_norm_act, _ext.relu_group_norm = fused["group_norm_act"], fused["relu_group_norm"]
+
+
+# ------------------------------------------------------------------------------------------------ Chamfer decisions
+class ChamferTape:
+    """`terms`: one dict per Chamfer term of a loss, in call order -- "idx_gt" (B, n_gt) / "idx_out" (B, n_out) int64:
+    the nearest neighbour of every gt point in the output cloud and of every output point in gt, as the recording run's
+    K = 1 search chose them; "out" (B, n_out, 3) / "gt" (B, n_gt, 3): the clouds that search saw, in double."""
+
+    def __init__(self, terms=()):
+        self.terms = list(terms)
+
+    def __len__(self):
+        return len(self.terms)
+
+    def same_decisions(self, other):
+        return len(self) == len(other) and all(torch.equal(a[k], b[k]) for a, b in zip(self.terms, other.terms)
+                                               for k in ("idx_gt", "idx_out"))
+
+
+def taped_sq_dists(output, gt, idx_gt, idx_out):
+    """(d_gt (B, n_gt), d_out (B, n_out)): |gt_i - output_idx_gt(i)|^2 and |output_j - gt_idx_out(j)|^2 in the dtype of
+    the clouds, by torch indexing alone -- differentiable in both clouds, no search."""
+    def direction(queries, points, idx):
+        rows = points.gather(1, idx.to(points.device).unsqueeze(-1).expand(-1, -1, 3))
+        return ((queries - rows) ** 2).sum(-1)
+    return direction(gt, output, idx_gt), direction(output, gt, idx_out)
+
+
+def taped_cd(output, gt, idx_gt, idx_out):
+    """calc_cd's (cd_p, cd_t), each (B,), from `taped_sq_dists`."""
+    d1, d2 = taped_sq_dists(output, gt, idx_gt, idx_out)
+    return (torch.sqrt(d1).mean(1) + torch.sqrt(d2).mean(1)) / 2, d1.mean(1) + d2.mean(1)
+
+
+@contextlib.contextmanager
+def chamfer_tape(mode, tape=None, nn=None):
+    """Pin the nearest-neighbour assignment of a Chamfer loss: the one decision that depends on the network's output,
+    so the one the shared geometry and the ReLU tape leave open.  Yields an object whose `.cd(fn)` is the
+    `(output, gt) -> (cd_p, cd_t)` a loss calls once per term.
+
+    mode "record": `.cd(fn)` runs `nn(gt, output)` -- the K = 1 search in both directions, `_ext.chamfer_nn`'s
+    signature and return order -- on the detached clouds, appends its two index tensors (and the clouds) to a new
+    tape, then returns `fn(output, gt)`: calc_cd, calc_cd_fused (which returns no index: the extra search finds the
+    same ones, its minima are chamfer_nn's bit for bit) or anything with their signature.  `.tape` is the tape.
+    mode "replay": `.cd()` consumes the next term of `tape` and evaluates it by `taped_cd` on the clouds it is given
+    (same shapes, or an AssertionError that names the term) -- no search, no `_ext` entry; `.outputs` collects the
+    output clouds it saw (detached, on the CPU).  Leaving the context with terms left over is an error."""
+    if mode not in ("record", "replay") or (mode == "replay") != (tape is not None) or (mode == "record") != (nn is not None):
+        raise ValueError("chamfer_tape('record', nn=search) or chamfer_tape('replay', tape)")
+
+    class Handle:
+        pass
+    h = Handle()
+    if mode == "record":
+        h.tape = ChamferTape()
+
+        def cd(fn):
+            def recorded(output, gt):
+                o, g = output.detach().contiguous(), gt.detach().contiguous()
+                _, idx_gt, _, idx_out = nn(g, o)
+                h.tape.terms.append({"idx_gt": idx_gt.detach().long().cpu(), "idx_out": idx_out.detach().long().cpu(),
+                                     "out": o.double().cpu(), "gt": g.double().cpu()})
+                return fn(output, gt)
+            return recorded
+        h.cd = cd
+        yield h
+    else:
+        h.tape, h.outputs = tape, []
+
+        def cd(fn=None):
+            def replayed(output, gt):
+                n = len(h.outputs)
+                assert n < len(tape), "chamfer_tape: Chamfer term %d, the tape holds %d" % (n, len(tape))
+                term = tape.terms[n]
+                assert output.shape == term["out"].shape and gt.shape == term["gt"].shape, \
+                    "chamfer_tape: term %d was recorded on %s / %s, replayed on %s / %s" % (
+                        n, tuple(term["out"].shape), tuple(term["gt"].shape), tuple(output.shape), tuple(gt.shape))
+                h.outputs.append(output.detach().double().cpu())
+                return taped_cd(output, gt, term["idx_gt"], term["idx_out"])
+            return replayed
+        h.cd = cd
+        yield h
+        assert len(h.outputs) == len(tape), "chamfer_tape: the replay ended at term %d of %d" % (len(h.outputs), len(tape))
+
+
+def oracle_chamfer_nn(x, y):
+    """`_ext.chamfer_nn`'s signature and return order on the CPU oracle (its K = 1 kNN, both directions, on the fp32
+    cast of the clouds): the search a `chamfer_tape("record")` takes where no GPU is."""
+    from oracle import pdr_oracle as O
+    a, b = _xyz32(x).cpu().numpy(), _xyz32(y).cpu().numpy()
+    out = []
+    for p, q in ((a, b), (b, a)):
+        d, i = O.knn(p, q, 1)
+        out += [torch.from_numpy(np.ascontiguousarray(d[..., 0])), torch.from_numpy(np.ascontiguousarray(i[..., 0])).long()]
+    return tuple(out)
+
+
+def chamfer_tape_honesty(tape, outputs64):
+    """The honesty condition of a replayed Chamfer tape.  `outputs64`: the float64 output cloud of every term (the
+    replay's `.outputs`).  A taped index j may differ from float64's own argmin j* only where the recording run could
+    not tell them apart.  With delta = the largest Euclidean distance between an output point of the recording run and
+    the same point in float64, moving one endpoint of a pair by at most delta changes its squared distance d by at most
+    2 sqrt(d) delta + delta^2; the recording run ranked j no worse than j*, and both distances move; its own fp32
+    evaluation of the distance it ranked is within 16 * 2^-24 relative.  So, in float64 on the float64 clouds,
+        d(j) - d(j*) <= 2 (2 sqrt(d(j)) delta + delta^2) + 16 * 2^-24 * d(j)
+    for every query with j != j*, in both directions.
+    -> {"differing": queries with j != j*, "ratio": the largest (d(j) - d(j*)) / bound over them (0.0 if none),
+        "delta": the largest delta over the terms, "nearest": the smallest float64 nearest-neighbour DISTANCE (not
+        squared) over all terms and both directions}"""
+    assert len(tape) == len(outputs64) > 0
+    differing, ratio, delta_max, nearest = 0, 0.0, 0.0, float("inf")
+    for term, out in zip(tape.terms, outputs64):
+        gt = term["gt"]
+        delta = float((out - term["out"]).norm(dim=-1).max())
+        delta_max = max(delta_max, delta)
+        pair = ((gt.unsqueeze(2) - out.unsqueeze(1)) ** 2).sum(-1)          # (B, n_gt, n_out), float64, term by term
+        for d_all, idx in ((pair, term["idx_gt"]), (pair.transpose(1, 2), term["idx_out"])):
+            best = d_all.min(-1).values
+            taped = d_all.gather(2, idx.unsqueeze(-1))[..., 0]
+            nearest = min(nearest, float(best.min().sqrt()))
+            other = taped > best                                            # (an exact float64 tie is the same minimum)
+            bound = 2 * (2 * taped.sqrt() * delta + delta ** 2) + 16 * 2.0 ** -24 * taped
+            differing += int(other.sum())
+            if bool(other.any()):
+                ratio = max(ratio, float(((taped - best) / bound)[other].max()))
+    return {"differing": differing, "ratio": ratio, "delta": delta_max, "nearest": nearest}
 
 
 @contextlib.contextmanager

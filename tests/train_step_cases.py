@@ -58,10 +58,14 @@ def inputs(regime, seed):
     return x, cond, target, torch.tensor(TS), torch.tensor(LABELS)
 
 
-def step(model, data, leaf=False):
+def step(model, data, leaf=False, loss_fn=None):
     """One step of `model` on `data` (as `inputs` returns it, on the model's device; floats are cast to the model's
     dtype) -> {"out": (B, N, 3), "grads": {parameter name: tensor, "x": coordinate gradient if `leaf`},
-    "records": {block: tensor}}, everything detached, double, on the CPU."""
+    "records": {block: tensor}}, everything detached, double, on the CPU.
+
+    loss_fn: None = the stage-one loss, MSE against `target`.  Else `loss_fn(out, x, target)` -> scalar, with `ts` of
+    `data` None for a network without step embedding (the stage-two step, tests/refine_step_cases.py); the result then
+    also holds "loss" and "out_grad", the gradient w.r.t. the network output (retained)."""
     x, cond, target, ts, label = data
     dtype = next(model.parameters()).dtype
     model.zero_grad(set_to_none=True)
@@ -73,23 +77,41 @@ def step(model, data, leaf=False):
                 out = model(x, cond.to(dtype), ts=ts, label=label)
         else:
             out = model(x, cond.to(dtype), ts=ts, label=label)
-    loss = ((out - target.to(dtype)) ** 2).mean()
+    if loss_fn is None:
+        loss = ((out - target.to(dtype)) ** 2).mean()
+    else:
+        out.retain_grad()
+        loss = loss_fn(out, x, target.to(dtype))
     loss.backward()
     grads = {n: (None if p.grad is None else p.grad.detach().double().cpu()) for n, p in model.named_parameters()}
     if leaf:
         grads["x"] = None if x_leaf.grad is None else x_leaf.grad.detach().double().cpu()
     model.zero_grad(set_to_none=True)
     records = {k: v.double().cpu() for k, v in rec.calls[-1].items() if k != "eps"}
-    return {"out": out.detach().double().cpu(), "grads": grads, "records": records}
+    result = {"out": out.detach().double().cpu(), "grads": grads, "records": records}
+    if loss_fn is not None:
+        result["loss"] = loss.detach().double().cpu()
+        result["out_grad"] = out.grad.detach().double().cpu()
+    return result
 
 
-def errors(got, want):
-    """-> {"out": e, "grad:<name>": e, "record:<block>": e} of one step against its float64 reference."""
+def top_scaled(want):
+    """The parameter gradients of a float64 step whose largest element is below 1e-3 of the network's largest gradient
+    element: those `errors` measures against that largest element."""
+    top = max(float(w.abs().max()) for n, w in want["grads"].items() if n != "x")
+    return {n for n, w in want["grads"].items() if float(w.abs().max()) < 1e-3 * top}
+
+
+def errors(got, want, top_scaled_names=None):
+    """-> {"out": e, "grad:<name>": e, "record:<block>": e} of one step against its float64 reference.
+    top_scaled_names: None = which gradients take the network's largest element as scale is decided on `want`
+    (`top_scaled`); a set = exactly these do, whatever `want` says -- for two runs with references of their own whose
+    errors are compared with each other (tests/test_refine_step_f64_gpu.py)."""
     top = max(float(w.abs().max()) for n, w in want["grads"].items() if n != "x")
     e = {"out": float((got["out"] - want["out"]).abs().max()) / float(want["out"].abs().max())}
     for n, w in want["grads"].items():
         scale = float(w.abs().max())
-        if scale < 1e-3 * top:
+        if (scale < 1e-3 * top) if top_scaled_names is None else (n in top_scaled_names):
             scale = top
         e["grad:" + n] = float((got["grads"][n] - w).abs().max()) / scale
     for n, w in want["records"].items():
