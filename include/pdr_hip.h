@@ -73,7 +73,10 @@ typedef void *pdr_stream_t; /* hipStream_t */
  *                pdr_query_group_cf / pdr_query_group_cf_grad are new; pdr_knn_group_cf_workspace_bytes /
  *                pdr_knn_group_cf_plan / pdr_knn_group_cf / pdr_knn_group_cf_grad are new;
  *                pdr_relu_group_norm_cf_workspace_bytes / pdr_relu_group_norm_cf_plan / pdr_relu_group_norm_cf /
- *                pdr_relu_group_norm_cf_grad are new; pdr_group_norm_act_add / pdr_group_norm_act_add_grad are new. */
+ *                pdr_relu_group_norm_cf_grad are new; pdr_group_norm_act_add / pdr_group_norm_act_add_grad are new;
+ *                pdr_relu_group_norm_conv_cf_workspace_bytes / pdr_relu_group_norm_conv_cf_plan /
+ *                pdr_relu_group_norm_conv_cf / pdr_relu_group_norm_conv_cf_grad_input /
+ *                pdr_relu_group_norm_conv_cf_grad_weight are new. */
 int pdr_version(void);
 /* last hip error string seen by this thread after a PDR_ELAUNCH ("" if none) */
 const char *pdr_last_error(void);
@@ -506,6 +509,54 @@ size_t pdr_relu_group_norm_cf_workspace_bytes(int B, int C1, int C2, int N, int 
  * aligned.  out = {family (0 scalar, 1 vector), k partitions per slab P, elements per partition E, Cg}.
  * C1 < 0, C2, N, K or G < 1, C1 + C2 < G or a NULL out: PDR_EINVAL; C N K >= 2^31 or C >= 2^24: PDR_EUNSUPPORTED. */
 int pdr_relu_group_norm_cf_plan(int C1, int C2, int N, int K, int G, int aligned16, long out[4]);
+/* A whole link of AttentionModule's score head on the TRAINABLE path ([ReLU, MyGroupNorm, Conv2d 1x1] over the virtual
+ * cat of pdr_relu_group_norm_cf) as one differentiable op whose fp32 MFMA GEMM normalises its operand as it loads it:
+ * the normalised tensor (B,C,N,K) is never written, read back or saved.  q, k, gamma, beta, mean, rstd and every size
+ * as pdr_relu_group_norm_cf; W (Cout,C) row-major f32 (the Conv2d weight viewed 2-D), bias (Cout) f32 or NULL
+ *     ->  out (B,Cout,N,K) f32 dense;  mean, rstd (B,G) f32 with the bits pdr_relu_group_norm_cf writes (both required).
+ * With xn[b,c,n,j] exactly the value pdr_relu_group_norm_cf writes to y (same statistics kernel, same element chain:
+ * csrc/relu_group_norm.h), the GEMM is defined bit for bit:
+ *     acc = +0;  for c = 0 .. C-1 ascending: acc = fma(W[o,c], xn[b,c,n,j], acc);  out = bias ? fl(acc + bias[o]) : acc
+ * (v_mfma_f32_32x32x2_f32 with its k index walking c in order; the LDS chunks of 16 channels continue the chain).
+ * THREE launches (statistics partials, mean / rstd, GEMM), no atomics, no allocation, no synchronisation: capturable;
+ * the same input gives the same bits, and cloud b of a batched call has the bits of the B = 1 call on that cloud.
+ *   - families: vector (K % 4 == 0 and k 16-byte aligned: 16-byte loads) and scalar; out is stored dword by dword.
+ *   - workspace: pdr_relu_group_norm_conv_cf_workspace_bytes bytes, 8-byte aligned, the caller's; it serves the forward
+ *     and pdr_relu_group_norm_conv_cf_grad_weight.
+ *   - validation, on the host before any launch, in this order: B, C1, N or K negative, C2 < 1, G < 1, Cout < 1, eps
+ *     negative or NaN: PDR_EINVAL; C1 + C2 < G: PDR_EINVAL; B N K == 0: PDR_OK, nothing launched, no pointer looked at;
+ *     B C N K >= 2^31, B Cout N K >= 2^31, B C >= 2^24, C > 1024, Cout > 1024 or B > 4095: PDR_EUNSUPPORTED; a NULL
+ *     k / W / out / mean / rstd / workspace, C1 > 0 with a NULL q, or exactly one of gamma / beta NULL: PDR_EINVAL. */
+int pdr_relu_group_norm_conv_cf(const float *q, const float *k, const float *gamma, const float *beta, const float *W,
+                                const float *bias, int B, int C1, int C2, int N, int K, int G, int Cout, float eps,
+                                float *out, float *mean, float *rstd, void *workspace, pdr_stream_t stream);
+/* Input gradient of the GEMM above, bit-defined the same way over the other index:
+ *     acc = +0;  for o = 0 .. Cout-1 ascending: acc = fma(W[o,c], grad_out[b,o,n,j], acc);  grad_xn[b,c,n,j] = acc
+ * grad_out (B,Cout,N,K) -> grad_xn (B,C,N,K), fully written: what pdr_relu_group_norm_cf_grad takes as grad_y.  ONE
+ * launch, no prologue, no workspace.  Vector family: K % 4 == 0 and grad_out 16-byte aligned.  B, N or K negative, C
+ * or Cout < 1: PDR_EINVAL; B N K == 0: PDR_OK; the limits above: PDR_EUNSUPPORTED; a NULL pointer: PDR_EINVAL. */
+int pdr_relu_group_norm_conv_cf_grad_input(const float *W, const float *grad_out, int B, int C, int N, int K, int Cout,
+                                           float *grad_xn, pdr_stream_t stream);
+/* Weight and bias gradients: grad_W[o,c] = sum_{b,n,j} grad_out[b,o,n,j] xn[b,c,n,j] with xn recomputed from q, k and
+ * the SAVED mean / rstd (the forward's bits), grad_bias[o] = sum grad_out.  Either may be NULL (not wanted); both NULL:
+ * PDR_EINVAL.  Order-fixed, no atomics: the N K positions of a cloud are cut into R ranges of L positions (the plan
+ * reports both; from N K alone); a workgroup accumulates one (cloud, range) of a tile of grad_W in one fp32 MFMA chain
+ * from +0 and writes the partial to the workspace; the B R partials of an element are added in DOUBLE in ascending
+ * (b, range) order and rounded once.  grad_bias: double sums of a (b, o, range) (thread t of 256 takes positions t,
+ * t + 256, .., then the block sum of pdr_relu_group_norm_cf), then the same fold.  Up to FOUR launches; capturable.
+ * Vector family: K % 4 == 0 and k, grad_out 16-byte aligned.  Validation as the forward (no eps), then the pointers. */
+int pdr_relu_group_norm_conv_cf_grad_weight(const float *q, const float *k, const float *gamma, const float *beta,
+                                            const float *mean, const float *rstd, const float *grad_out, int B, int C1,
+                                            int C2, int N, int K, int G, int Cout, float *grad_W, float *grad_bias,
+                                            void *workspace, pdr_stream_t stream);
+/* Bytes of workspace the forward or the weight gradient needs (the larger: B G (P + 1) pairs of doubles; B R Cout C
+ * floats + B R Cout doubles); 0 for an empty, invalid or unsupported problem.  Host only. */
+size_t pdr_relu_group_norm_conv_cf_workspace_bytes(int B, int C1, int C2, int N, int K, int G, int Cout);
+/* The decision the calls above read.  Host only.  out = {family (0 scalar, 1 vector), P, E, Cg (the statistics plan of
+ * pdr_relu_group_norm_cf_plan), positions per workgroup of the GEMMs, positions per weight-gradient chain L, ranges
+ * per cloud R, output rows per workgroup of the forward GEMM}.  Errors as pdr_relu_group_norm_cf_plan, and Cout < 1:
+ * PDR_EINVAL; the forward's limits (with B = 1): PDR_EUNSUPPORTED. */
+int pdr_relu_group_norm_conv_cf_plan(int C1, int C2, int N, int K, int G, int Cout, int aligned16, long out[8]);
 /* Neighbourhood grouping of the TRAINABLE path: what QueryAndGroup.forward (pointnet2_ops/pointnet2_utils.py) does
  * after its neighbour search, channel-first, as one differentiable op (the inference path gathers channel-last in
  * pdr_group_build):

@@ -60,6 +60,12 @@ SIGNATURES = {
     "pdr_relu_group_norm_cf_plan": (_I, [_I, _I, _I, _I, _I, _I, _P]),
     "pdr_relu_group_norm_cf": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _P, _P, _P, _P, _P]),
     "pdr_relu_group_norm_cf_grad": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
+    "pdr_relu_group_norm_conv_cf_workspace_bytes": (_Z, [_I, _I, _I, _I, _I, _I, _I]),
+    "pdr_relu_group_norm_conv_cf_plan": (_I, [_I, _I, _I, _I, _I, _I, _I, _P]),
+    "pdr_relu_group_norm_conv_cf": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _F, _P, _P, _P, _P, _P]),
+    "pdr_relu_group_norm_conv_cf_grad_input": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P]),
+    "pdr_relu_group_norm_conv_cf_grad_weight": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P,
+                                                     _P]),
     "pdr_query_group_cf_workspace_bytes": (_Z, [_I, _I, _I, _I]),
     "pdr_query_group_cf_plan": (_I, [_I, _I, _I, _I, _I, _I, _P]),
     "pdr_query_group_cf": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P]),

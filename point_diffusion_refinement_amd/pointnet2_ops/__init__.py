@@ -17,9 +17,12 @@ never builds the cat.
 `set_fused_injection(True | False)` (default False) makes `Mlp_plus_t_emb` fold the embedding it adds behind each of its
 [conv, MyGroupNorm, act] stacks, and the residual behind the last one, into the stack's last norm and activation: the
 one op `pointnet2_utils.group_norm_act_add` instead of the norm, the activation, the broadcast adds and the residual
-add."""
+add.
+`set_fused_score_conv(True | False)` (default False) makes `AttentionModule` run each [ReLU, MyGroupNorm, Conv2d 1x1]
+link of its score head as the one op `pointnet2_utils.relu_group_norm_conv`, whose fp32 MFMA GEMM normalises its
+operand as it loads it: neither the cat nor the normalised tensor is built or saved."""
 from . import pointnet2_modules, pointnet2_utils  # noqa: F401
 from ._ext import (is_deterministic, is_fused_attention_pool, is_fused_group_norm, is_fused_grouping,  # noqa: F401
-                   is_fused_injection, is_fused_knn_grouping, is_fused_score_norm, set_deterministic,
-                   set_fused_attention_pool, set_fused_group_norm, set_fused_grouping, set_fused_injection,
-                   set_fused_knn_grouping, set_fused_score_norm)
+                   is_fused_injection, is_fused_knn_grouping, is_fused_score_conv, is_fused_score_norm,
+                   set_deterministic, set_fused_attention_pool, set_fused_group_norm, set_fused_grouping,
+                   set_fused_injection, set_fused_knn_grouping, set_fused_score_conv, set_fused_score_norm)

@@ -9,6 +9,8 @@ allocates the outputs as torch tensors and forwards raw device pointers plus the
 CURRENT stream to libpdr_hip.so.  CPU tensors are rejected exactly like the
 reference ("CPU not supported", sampling.cpp:34): there is no CPU fallback.
 """
+import ctypes
+
 import torch
 
 from .. import _lib
@@ -161,6 +163,27 @@ def set_fused_score_norm(mode):
 def is_fused_score_norm():
     """Whether AttentionModule's score head takes the fused ReLU + GroupNorm op right now."""
     return _fused_score_norm
+
+
+_fused_score_conv = False         # set_fused_score_conv: the score head's links run pdr_relu_group_norm_conv_cf
+
+
+def set_fused_score_conv(mode):
+    """Process-wide switch: True = `AttentionModule.forward` skips the expand and the cat of its score head and runs each
+    [ReLU, MyGroupNorm, Conv2d 1x1] link of `weight_conv` as one `relu_group_norm_conv` op (and its backward), which
+    never builds the normalised tensor, for fp32 GPU tensors of a shape the kernels support; a link they do not take
+    runs as it does under `set_fused_score_norm`.  False (the default) = as ever.  Independent of the other switches.
+    Returns the previous setting."""
+    global _fused_score_conv
+    if not isinstance(mode, bool):
+        raise TypeError("set_fused_score_conv takes True or False, got %r" % (mode,))
+    prev, _fused_score_conv = _fused_score_conv, mode
+    return prev
+
+
+def is_fused_score_conv():
+    """Whether AttentionModule's score head takes the fused ReLU + GroupNorm + conv op right now."""
+    return _fused_score_conv
 
 
 _fused_injection = False          # set_fused_injection: Mlp_plus_t_emb's adds run inside pdr_group_norm_act_add
@@ -838,6 +861,126 @@ def relu_group_norm_grad(q, k, weight, bias, mean, rstd, grad_y, num_groups, nee
                                                            C2, N, K, G, _ptr(gq), _ptr(gk), _ptr(gw), _ptr(gb),
                                                            ws.data_ptr(), _stream()), "relu_group_norm_grad")
     return gq, gk, gw, gb
+
+
+def _req_relu_group_norm_conv(q, k, weight, bias, num_groups, conv_weight, conv_bias):
+    """Shapes and dtypes of relu_group_norm_conv's inputs; returns (B, C1, C2, N, K, G, Cout)."""
+    B, C1, C2, N, K, G = _req_relu_group_norm(q, k, weight, bias, num_groups)
+    _req(conv_weight, "conv_weight", torch.float32)
+    _same_device(k, conv_weight)
+    if conv_weight.dim() != 2 or int(conv_weight.shape[1]) != C1 + C2:
+        raise RuntimeError("conv_weight must have shape (Cout, C1 + C2) = (Cout, %d), got %s"
+                           % (C1 + C2, tuple(conv_weight.shape)))
+    Cout = int(conv_weight.shape[0])
+    if conv_bias is not None:
+        _req(conv_bias, "conv_bias", torch.float32)
+        _same_device(k, conv_bias)
+        if tuple(conv_bias.shape) != (Cout,):
+            raise RuntimeError("conv_bias must have shape (Cout,) = (%d,), got %s" % (Cout, tuple(conv_bias.shape)))
+    return B, C1, C2, N, K, G, Cout
+
+
+def _relu_group_norm_conv_workspace(B, C1, C2, N, K, G, Cout, device):
+    nbytes = _lib.load().pdr_relu_group_norm_conv_cf_workspace_bytes(B, C1, C2, N, K, G, Cout)
+    return torch.empty(max(nbytes // 8, 1), dtype=torch.float64, device=device)
+
+
+def relu_group_norm_conv_supported(C1, k_shape, num_groups, Cout):
+    """Whether pdr_relu_group_norm_conv_cf and its two gradients take q (B, C1, N) (C1 = 0: no q), k of shape
+    (B, C2, N, K) and a (Cout, C1 + C2) weight: what relu_group_norm_supported asks, at most 1024 channels on either
+    side of the convolution, at most 4095 clouds and fewer than 2^31 output elements."""
+    if not relu_group_norm_supported(C1, k_shape, num_groups):
+        return False
+    B, C2, N, K = (int(d) for d in k_shape)
+    Cout = int(Cout)
+    return 1 <= Cout <= 1024 and int(C1) + C2 <= 1024 and B <= 4095 and B * Cout * N * K < 2 ** 31
+
+
+def relu_group_norm_conv(q, k, weight, bias, num_groups, eps, conv_weight, conv_bias):
+    """conv1x1(MyGroupNorm(relu(cat([q broadcast over K, k], 1)))) in three launches (pdr_relu_group_norm_conv_cf)
+    without the cat and without the normalised tensor: q, k, weight, bias as relu_group_norm, conv_weight (Cout, C)
+    f32, conv_bias (Cout) f32 or None -> (out (B, Cout, N, K), mean (B, G), rstd (B, G))."""
+    B, C1, C2, N, K, G, Cout = _req_relu_group_norm_conv(q, k, weight, bias, num_groups, conv_weight, conv_bias)
+    out = torch.empty((B, Cout, N, K), dtype=torch.float32, device=k.device)
+    mean = torch.empty((B, max(G, 0)), dtype=torch.float32, device=k.device)
+    rstd = torch.empty_like(mean)
+    ws = _relu_group_norm_conv_workspace(B, C1, C2, N, K, G, Cout, k.device)
+    with torch.cuda.device(k.device):
+        _lib.check(_lib.load().pdr_relu_group_norm_conv_cf(_ptr(q), k.data_ptr(), _ptr(weight), _ptr(bias),
+                                                           conv_weight.data_ptr(), _ptr(conv_bias), B, C1, C2, N, K, G,
+                                                           Cout, float(eps), out.data_ptr(), mean.data_ptr(),
+                                                           rstd.data_ptr(), ws.data_ptr(), _stream()),
+                   "relu_group_norm_conv")
+    return out, mean, rstd
+
+
+def relu_group_norm_conv_grad_input(conv_weight, grad_out):
+    """grad_out (B, Cout, N, K) f32, conv_weight (Cout, C) f32 -> the gradient (B, C, N, K) of the normalised tensor
+    (pdr_relu_group_norm_conv_cf_grad_input, one launch): what relu_group_norm_grad takes as grad_y."""
+    _req(conv_weight, "conv_weight", torch.float32)
+    _req(grad_out, "grad_out", torch.float32)
+    _same_device(grad_out, conv_weight)
+    if conv_weight.dim() != 2 or grad_out.dim() != 4 or int(grad_out.shape[1]) != int(conv_weight.shape[0]):
+        raise RuntimeError("relu_group_norm_conv_grad_input: conv_weight (Cout, C) and grad_out (B, Cout, N, K), got "
+                           "%s and %s" % (tuple(conv_weight.shape), tuple(grad_out.shape)))
+    B, Cout, N, K = (int(d) for d in grad_out.shape)
+    C = int(conv_weight.shape[1])
+    gxn = torch.empty((B, C, N, K), dtype=torch.float32, device=grad_out.device)
+    with torch.cuda.device(grad_out.device):
+        _lib.check(_lib.load().pdr_relu_group_norm_conv_cf_grad_input(conv_weight.data_ptr(), grad_out.data_ptr(), B, C,
+                                                                      N, K, Cout, gxn.data_ptr(), _stream()),
+                   "relu_group_norm_conv_grad_input")
+    return gxn
+
+
+def relu_group_norm_conv_grad_weight(q, k, weight, bias, mean, rstd, grad_out, num_groups, need_weight=True,
+                                     need_bias=True, return_partials=False):
+    """Gradients of the convolution's weight (Cout, C) and bias (Cout) (pdr_relu_group_norm_conv_cf_grad_weight): the
+    normalised values are recomputed from q, k and the saved (B, G) statistics.  -> (grad_conv_weight,
+    grad_conv_bias), None where not needed (at least one must be).  return_partials=True appends the fp32 partials
+    (B, R, Cout, C) the fold added up (a view of the call's workspace; None without the weight gradient)."""
+    B, C1, C2, N, K, G = _req_relu_group_norm(q, k, weight, bias, num_groups)
+    _req(grad_out, "grad_out", torch.float32)
+    if grad_out.dim() != 4 or tuple(grad_out.shape[0:1] + grad_out.shape[2:]) != (B, N, K):
+        raise RuntimeError("grad_out must have shape (B, Cout, N, K) = (%d, Cout, %d, %d), got %s"
+                           % (B, N, K, tuple(grad_out.shape)))
+    Cout = int(grad_out.shape[1])
+    for t, name in ((mean, "mean"), (rstd, "rstd")):
+        _req(t, name, torch.float32)
+        if tuple(t.shape) != (B, G):
+            raise RuntimeError("%s must have shape (B, G) = (%d, %d), got %s" % (name, B, G, tuple(t.shape)))
+    _same_device(k, grad_out, mean, rstd)
+    C = C1 + C2
+    gw = torch.empty((Cout, C), dtype=torch.float32, device=k.device) if need_weight else None
+    gb = torch.empty((Cout,), dtype=torch.float32, device=k.device) if need_bias else None
+    if B * N * K == 0:                                        # the empty problem launches nothing: a sum of nothing
+        for t in (gw, gb):
+            if t is not None:
+                t.zero_()
+    ws = _relu_group_norm_conv_workspace(B, C1, C2, N, K, G, Cout, k.device)
+    with torch.cuda.device(k.device):
+        _lib.check(_lib.load().pdr_relu_group_norm_conv_cf_grad_weight(_ptr(q), k.data_ptr(), _ptr(weight), _ptr(bias),
+                                                                       mean.data_ptr(), rstd.data_ptr(),
+                                                                       grad_out.data_ptr(), B, C1, C2, N, K, G, Cout,
+                                                                       _ptr(gw), _ptr(gb), ws.data_ptr(), _stream()),
+                   "relu_group_norm_conv_grad_weight")
+    if not return_partials:
+        return gw, gb
+    parts = None
+    if gw is not None and B * N * K > 0:
+        R = relu_group_norm_conv_plan(C1, C2, N, K, G, Cout)["R"]
+        parts = ws.view(torch.float32)[:B * R * Cout * C].view(B, R, Cout, C)
+    return gw, gb, parts
+
+
+def relu_group_norm_conv_plan(C1, C2, N, K, num_groups, Cout, aligned16=True):
+    """pdr_relu_group_norm_conv_cf_plan as a dict: family (0 scalar, 1 vector), P, E, Cg (the statistics plan), tile
+    (positions per workgroup of the GEMMs), L (positions per weight-gradient chain), R (ranges per cloud), rows
+    (output rows per workgroup of the forward GEMM)."""
+    out = (ctypes.c_long * 8)()
+    _lib.check(_lib.load().pdr_relu_group_norm_conv_cf_plan(int(C1), int(C2), int(N), int(K), int(num_groups), int(Cout),
+                                                            int(bool(aligned16)), out), "relu_group_norm_conv_plan")
+    return dict(zip(("family", "P", "E", "Cg", "tile", "L", "R", "rows"), (int(v) for v in out)))
 
 
 QUERY_GROUP_USE_XYZ, QUERY_GROUP_ABS, QUERY_GROUP_CENTER = 1, 2, 4     # the `flags` bits of pdr_query_group_cf

@@ -12,7 +12,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _ext
-from .pointnet2_utils import attention_pool, group_norm_act, group_norm_act_add, relu_group_norm
+from .pointnet2_utils import attention_pool, group_norm_act, group_norm_act_add, relu_group_norm, \
+    relu_group_norm_conv
 
 
 class MyGroupNorm(nn.Module):
@@ -157,7 +158,7 @@ class AttentionModule(nn.Module):
         """feat (B,C_in1,N), grouped_feat (B,C_in2,N,K) -> scores (B,C_out,N,K): weight_conv over
         [feat_conv(query) repeated over K | grouped_feat_conv(key)]."""
         K = grouped_feat.shape[-1]
-        if _ext._fused_score_norm:                        # read directly: with the switch off this path calls nothing
+        if _ext._fused_score_norm or _ext._fused_score_conv:   # read directly: with both off this path calls nothing
             scores = self._fused_score_head(feat, grouped_feat)
             if scores is not None:
                 return scores
@@ -168,7 +169,10 @@ class AttentionModule(nn.Module):
     def _fused_score_head(self, feat, grouped_feat):
         """The score head without the expand and the cat, each [ReLU, MyGroupNorm] pair of weight_conv as one
         `relu_group_norm` op (set_fused_score_norm, default off); None where that does not apply: no norms
-        (attention_bn=False), tensors that are not fp32 on the GPU, or a shape the kernels do not take."""
+        (attention_bn=False), tensors that are not fp32 on the GPU, or a shape the kernels do not take.
+        With set_fused_score_conv (default off) a whole [ReLU, MyGroupNorm, Conv2d] link whose shape
+        `relu_group_norm_conv_supported` accepts is one `relu_group_norm_conv` op with the Conv2d's own weight and
+        bias; a link it does not accept runs as above under set_fused_score_norm, else as the composition."""
         wc = self.weight_conv
         if len(wc) != 6 or not (isinstance(wc[1], MyGroupNorm) and isinstance(wc[4], MyGroupNorm)):
             return None
@@ -180,12 +184,27 @@ class AttentionModule(nn.Module):
         if not (_ext.relu_group_norm_supported(C1, (B, C2, N, K), wc[1].num_groups)
                 and _ext.relu_group_norm_supported(0, (B, wc[2].out_channels, N, K), wc[4].num_groups)):
             return None
+        conv_on, norm_on = _ext._fused_score_conv, _ext._fused_score_norm
+        as_conv = [conv_on and _ext.relu_group_norm_conv_supported(c1, (B, c2, N, K), wc[i].num_groups,
+                                                                    wc[i + 1].out_channels)
+                   for i, c1, c2 in ((1, C1, C2), (4, 0, wc[2].out_channels))]
+        if not norm_on and not any(as_conv):
+            return None
         q = self.feat_conv(feat.unsqueeze(-1)).squeeze(-1)
-        k = self.grouped_feat_conv(grouped_feat)
-        gn = wc[1].group_norm
-        h = wc[2](relu_group_norm(k, gn.weight, gn.bias, wc[1].num_groups, gn.eps, q=q))
-        gn = wc[4].group_norm
-        return wc[5](relu_group_norm(h, gn.weight, gn.bias, wc[4].num_groups, gn.eps))
+        h = self.grouped_feat_conv(grouped_feat)
+        for i, fused in ((1, as_conv[0]), (4, as_conv[1])):
+            gn, conv = wc[i].group_norm, wc[i + 1]
+            if fused:
+                h = relu_group_norm_conv(h, gn.weight, gn.bias, wc[i].num_groups, gn.eps,
+                                         conv.weight.view(conv.out_channels, -1), conv.bias, q=q)
+            elif norm_on:
+                h = conv(relu_group_norm(h, gn.weight, gn.bias, wc[i].num_groups, gn.eps, q=q))
+            else:                                         # the composition of this link
+                if q is not None:
+                    h = torch.cat([q.unsqueeze(-1).expand(-1, -1, -1, K), h], dim=1)
+                h = conv(wc[i](wc[i - 1](h)))
+            q = None
+        return h
 
     def forward(self, feat, grouped_feat, grouped_feat_out, count):
         """feat (B,C_in1,N) query; grouped_feat (B,C_in2,N,K) key; grouped_feat_out (B,C_out,N,K)

@@ -277,6 +277,58 @@ def relu_group_norm(k, weight, bias, num_groups, eps=1e-5, q=None):
     return ReluGroupNorm.apply(None if q is None else q.contiguous(), k.contiguous(), weight, bias, num_groups, eps)
 
 
+class ReluGroupNormConv(Function):
+    """conv1x1(MyGroupNorm(relu([q over K | k]))): _ext.relu_group_norm_conv.  Saves q, k, the (B, G) mean / rstd and
+    the parameters -- not the cat and not the normalised tensor, which never exists.  Backward: the weight gradient
+    (normalised values recomputed; first, so that its workspace and the buffer below are never alive together), the
+    input-gradient GEMM into a (B, C, N, K) buffer, then _ext.relu_group_norm_grad on the buffer, which is released
+    before the gradients are returned; the GEMM is skipped when none of q / k / weight / bias needs a gradient.  All
+    of it order-fixed."""
+
+    @staticmethod
+    def forward(ctx, q, k, weight, bias, conv_weight, conv_bias, num_groups, eps):
+        out, mean, rstd = _ext.relu_group_norm_conv(q, k, weight, bias, num_groups, eps, conv_weight, conv_bias)
+        ctx.num_groups, ctx.has_q, ctx.affine, ctx.has_cb = num_groups, q is not None, weight is not None, \
+            conv_bias is not None
+        ctx.save_for_backward(*[t for t in (k, mean, rstd, conv_weight, q, weight, bias) if t is not None])
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        saved = list(ctx.saved_tensors)
+        k, mean, rstd, conv_weight = saved[:4]
+        q = saved[4] if ctx.has_q else None
+        weight, bias = saved[-2:] if ctx.affine else (None, None)
+        need = ctx.needs_input_grad
+        need_q = ctx.has_q and need[0]
+        need_k = need[1]
+        need_w, need_b = (need[2], need[3]) if ctx.affine else (False, False)
+        need_cw, need_cb = need[4], ctx.has_cb and need[5]
+        grad_out = grad_out.contiguous().float()
+        gq = gk = gw = gb = gcw = gcb = None
+        if need_cw or need_cb:
+            gcw, gcb = _ext.relu_group_norm_conv_grad_weight(q, k, weight, bias, mean, rstd, grad_out, ctx.num_groups,
+                                                             need_cw, need_cb)
+        if need_q or need_k or need_w or need_b:
+            gxn = _ext.relu_group_norm_conv_grad_input(conv_weight, grad_out)
+            gq, gk, gw, gb = _ext.relu_group_norm_grad(q, k, weight, bias, mean, rstd, gxn, ctx.num_groups, need_q,
+                                                       need_k, need_w, need_b)
+            del gxn
+        return gq, gk, gw, gb, gcw, gcb, None, None
+
+
+def relu_group_norm_conv(k, weight, bias, num_groups, eps, conv_weight, conv_bias, q=None):
+    """k (B, C2, N, K) f32 on the GPU, q (B, C1, N) or None, weight / bias (C - C % num_groups) or both None,
+    conv_weight (Cout, C) or (Cout, C, 1, 1), conv_bias (Cout) or None, C = C1 + C2 ->
+    conv1x1(MyGroupNorm(relu(cat([q expanded over K, k], 1)))) (B, Cout, N, K) as one differentiable op
+    (pdr_relu_group_norm_conv_cf and its two gradient calls, then pdr_relu_group_norm_cf_grad): a whole
+    [ReLU, MyGroupNorm, Conv2d] link of AttentionModule.weight_conv without the cat and without the normalised tensor."""
+    conv_weight = conv_weight.reshape(conv_weight.shape[0], -1).contiguous()
+    return ReluGroupNormConv.apply(None if q is None else q.contiguous(), k.contiguous(), weight, bias, conv_weight,
+                                   conv_bias, num_groups, eps)
+
+
 class QueryGroup(Function):
     """xyz (B,n,3), new_xyz (B,m,3), features (B,C,n) | None, idx (B,m,K) i32, counts (B,m) i32 | None, flags ->
     (B, C + 3E, m, K): _ext.query_group.  Saves idx and counts only -- every output value is a copy or one difference

@@ -1,7 +1,8 @@
 """Forward plus backward of the whole DDPM network on the module (trainable) path with an MSE loss on its output: all
 five one-op switches off (set_fused_attention_pool, set_fused_group_norm, set_fused_grouping, set_fused_knn_grouping,
-set_fused_score_norm) against all five on, and against all five and set_fused_injection on (the setting "six", DESIGN
-7a.9).  DESIGN sections 7a.3 to 7a.7 each list this figure as not measured.
+set_fused_score_norm) against all five on, against all five and set_fused_injection on (the setting "six", DESIGN
+7a.9), and against those six and set_fused_score_conv on (the setting "seven").  DESIGN sections 7a.3 to
+7a.7 each list this figure as not measured.
 
 One child process per setting and round (--rounds > 1 alternates the settings: off, on, six, off, on, six, ..), each
 under its own time limit; the first child that fails ends the run.  In a child:
@@ -12,6 +13,7 @@ RESULT ({"oom": true}), not an error.
 
     python tools/train_step_bench.py [--B 8] [--reps 10] [--warmup 3] [--limit 300] [--settings off,on,six] [--rounds 1]
                                      [--out profiles/train_step_injection.json]
+    python tools/train_step_bench.py --settings off,six,seven --out profiles/train_step_score_conv.json
 """
 import argparse
 import json
@@ -26,7 +28,8 @@ if ROOT not in sys.path:
 
 SWITCHES = ("set_fused_attention_pool", "set_fused_group_norm", "set_fused_grouping", "set_fused_knn_grouping",
             "set_fused_score_norm")
-SETTINGS = {"off": (), "on": SWITCHES, "six": SWITCHES + ("set_fused_injection",)}
+SETTINGS = {"off": (), "on": SWITCHES, "six": SWITCHES + ("set_fused_injection",),
+            "seven": SWITCHES + ("set_fused_injection", "set_fused_score_conv")}
 
 
 def measure(setting, B, reps, warmup):
@@ -38,7 +41,7 @@ def measure(setting, B, reps, warmup):
         sys.exit("train_step_bench: no GPU (the module path has no CPU ops)")
     dev = torch.device("cuda:0")
     on = SETTINGS[setting]
-    for name in SETTINGS["six"]:
+    for name in SETTINGS["seven"]:
         getattr(pointnet2_ops, name)(name in on)
     torch.manual_seed(0)
     net = PointNet2CloudCondition(configs.ddpm_pointnet_config()).to(dev).train()
@@ -96,9 +99,9 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--limit", type=int, default=300, help="time limit of one child process, seconds")
     ap.add_argument("--out", default="")
-    ap.add_argument("--settings", default="off,on,six", help="comma-separated: off | on (five switches) | six")
+    ap.add_argument("--settings", default="off,on,six", help="comma-separated: off | on (five switches) | six | seven")
     ap.add_argument("--rounds", type=int, default=1, help="processes per setting, the settings alternating")
-    ap.add_argument("--one", default="", help="(child) measure one setting: off | on | six")
+    ap.add_argument("--one", default="", help="(child) measure one setting: off | on | six | seven")
     args = ap.parse_args()
     if args.one:
         print(json.dumps(measure(args.one, args.B, args.reps, args.warmup)), flush=True)
